@@ -21,6 +21,9 @@ collective runs once behind the last step on its own normal-priority stream, ins
 `--branch ripu|hyper`, `--feat-dtype f32`, `--channels 512`, `--source lowres` are variants for
 DESIGN.md / profiles/, not the BASELINE unit.
 
+`--dump-outputs DIR` writes what the last timed step computed (pick tables, counts, sampled score / impurity / uncertainty
+maps) as .npy files, so that two builds can be compared output for output on the same seeded inputs.
+
 Prints ONE JSON line (rank 0).  roofline: the feature-reduction kernel's algorithmic bytes / its
 average duration measured live with HIP events on its own stream.  cpu_baseline: the CPU oracle
 (OpenMP over the host cores this process may use) on 1 warm-up + 8 of the same images (kind "port").
@@ -50,6 +53,7 @@ from halo_amd import _lib as _halo_lib  # noqa: E402  (constants only; the libra
 LOGIT_LR_VALU_PER_PX = 1104.0      # SQ_INSTS_VALU per output pixel at 19 classes, profiles/r05_pmc_lowres.json (578.8 M per 16 images) (1162 before the integer forms, 1411 in round 3)
 HBM_PEAK_GBPS = 8000.0       # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
 H, W, O = 1024, 2048, 19
+DUMP_SAMPLE = 1 << 20        # --dump-outputs: elements kept per map (4 files x 8 MB at most + the pick tables)
 
 
 def parse():
@@ -89,6 +93,11 @@ def parse():
                          "fills on a housekeeping stream")
     ap.add_argument("--dump-tables", default="", help="rank 0 writes the round's gathered pick tables / counts / owners (pool "
                                                       "order) to this .npz after the timed region (tests compare world sizes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step handed its caller to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB): picks (b, regions, 3) and counts (b,) in full; score (the scorer's map, before the -inf of "
+                         "active pixels and picked windows), impurity and uncertainty as a fixed sample of at most %d elements of the flattened (b, H, W) maps, "
+                         "taken at sample_index (one seeded position per equal stride)" % DUMP_SAMPLE)
     ap.add_argument("--tail", choices=["auto", "split", "inline"], default="auto",
                     help="split = the scorer's tail kernels on their own stream, forked behind the feature pass (halo_score_maps_split), "
                          "so that they overlap the next step's feature kernel; inline = on the scoring stream, between two feature "
@@ -384,6 +393,48 @@ class Pipeline:
             elif not torch.equal(self.ref_tables[lo][:b], tab):
                 self.tables_consistent = False
 
+    def rescore(self, lo, b):
+        """FloatingRegionScore.forward on ring images [lo, lo + b) as a caller receives it -- before `score[active] = -inf` and
+        before the selection writes -inf into its windows, both of which the pipeline does in place -- with its impurity and
+        uncertainty maps.  Same calls as step(), on fresh buffers, outside the timed region."""
+        from halo_amd.core.active.floating_region import score_maps, score_maps_lowres
+        lb, fb, gb = self.logit[lo:lo + b], self.feat[lo:lo + b], self.gt[lo:lo + b]
+        if self.lowres:
+            return score_maps_lowres(lb, fb, self.size, self.unc, self.pur, self.norm, gb, ksize=3, K=self.K, c=1.0, want_maps=True,
+                                     mode=self.lr_mode)
+        return score_maps(lb, fb, self.unc, self.pur, self.norm, gb, size=3, K=self.K, c=1.0, want_maps=True)
+
+    def last_outputs(self, n_sample, seed=0):
+        """What the last step computed, on the host (after drain): the pick table and count of each of its b images, and the
+        score, impurity and uncertainty maps -- all of them, or at most `n_sample` elements of each flattened (b, H, W) map: one
+        position per equal stride, its offset in the stride drawn from `seed`.  The pipeline's score buffer ends the step with
+        -inf over the active pixels and every pick's window; the score written is the scorer's map before those writes
+        (rescore), checked to equal the timed buffer bit for bit wherever that is finite, next to the timed impurity and
+        uncertainty maps it must also equal."""
+        k = (self.step_no - 1) % self.D
+        lo, b = self.slot_lo[k]
+        tab, cnt = self.slot_out[k]
+        timed = self.score[k][:b]
+        score, imp, unc = self.rescore(lo, b)
+        fin = torch.isfinite(timed)
+        assert bool(torch.isneginf(timed[~fin]).all()), "the timed score map holds NaN or +inf"
+        assert torch.equal(score[fin], timed[fin]), "the re-scored map differs from the timed step's"
+        assert torch.equal(imp, self.imp) and torch.equal(unc, self.unc_map), "the re-scored maps differ from the timed step's"
+        maps = {"score": score, "impurity": self.imp, "uncertainty": self.unc_map}
+        numel = timed.numel()
+        if numel <= n_sample:
+            idx = np.arange(numel, dtype=np.int64)
+        else:
+            stride = numel // n_sample
+            idx = np.arange(n_sample, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, n_sample)
+        idx_d = torch.from_numpy(idx).to(self.dev)
+        out = {"picks": tab.double().cpu().numpy(), "counts": cnt.double().cpu().numpy(), "sample_index": idx.astype(np.float64)}
+        for name, m in maps.items():
+            assert m.numel() == numel, name
+            v = m.reshape(-1).index_select(0, idx_d)
+            out[name] = (v if v.dtype in (torch.float32, torch.float64) else v.double()).cpu().numpy()
+        return out
+
     def lowres_pass_ms(self):
         """per full-batch timed step of the low-res source: {logit, feat (embedding pass), gram, radius (the two kernels of the gram
         route; None otherwise), tail} -> list of ms"""
@@ -581,6 +632,8 @@ def main():
     # ---- the pool and this rank's block of it (halo_amd.pool.shard_range: contiguous ceil(N/world) images per rank)
     from halo_amd.pool import shard_range
     pool_mode = a.pool_images > 0
+    if not pool_mode and a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     n_pool = a.pool_images if pool_mode else world * a.steps * B
     lo_r, hi_r = shard_range(n_pool, rank, world)
     rows = math.ceil(n_pool / world)
@@ -622,6 +675,7 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0                                       # the clock stops here, on both sides of the barrier
     pipe.self_check()                                                   # host-synchronising checks: after it
+    dumped = pipe.last_outputs(DUMP_SAMPLE) if rank == 0 and a.dump_outputs and sched else None   # before anything else runs
     rank_dts = [dt_rank]
     if use_dist:
         cdev = torch.device("cpu") if host_backend else dev
@@ -878,6 +932,10 @@ def main():
             sys.exit("bench.py: the timed pipeline's pick tables differ from the CPU oracle's")
     if rank == 0 and a.dump_tables:
         np.savez(a.dump_tables, tables=tables.cpu().numpy(), counts=counts.cpu().numpy(), n_pool=n_pool, world=world)
+    if dumped is not None:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

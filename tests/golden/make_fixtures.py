@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = os.environ.get("HALO_REFERENCE", "/root/reference")
-OUT_DIR = os.environ.get("HALO_FIXTURE_OUT", HERE)      # tests/test_fixtures_reproduce.py regenerates into a temp dir
+OUT_DIR = os.environ.get("HALO_FIXTURE_OUT", HERE)      # another directory: regenerate and compare with the committed files
 
 
 def import_reference():
@@ -490,6 +490,7 @@ FULLSIZE = {
     "halo_c64_late_sat_peak_s3": (3, 64, "halo", ("late_round", "saturated", "peaked"), False),
     "ripu_s2": (2, 64, "ripu", (), False),
     "hyper_s1": (1, 64, "hyper", (), False),                                       # the reference's DEFAULT purity (defaults.py:69)
+    "hyper_late_s101": (101, 64, "hyper", ("late_round",), False),                 # the default purity in a later round
 }
 
 

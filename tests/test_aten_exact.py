@@ -27,6 +27,18 @@ import oracle.halo_oracle as ho
 from conftest import ROOT
 
 
+def mkl_log_is_avx512():
+    """Which of MKL's vsLn paths torch.log runs: the AVX-512 one needs an AVX-512 host (ATen's capability) AND an Intel processor --
+    MKL dispatches its AVX-512 kernels by CPU vendor, and an AVX-512 AMD host runs the AVX2 path."""
+    if torch.backends.cpu.get_cpu_capability() != "AVX512":
+        return False
+    try:
+        with open("/proc/cpuinfo") as f:
+            return any(ln.startswith("vendor_id") and "GenuineIntel" in ln for ln in f)
+    except OSError:
+        return False
+
+
 def bits_differ(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return int((~((a == b) | ((a != a) & (b != b)))).sum())
@@ -114,14 +126,14 @@ def test_oracle_logf_is_correctly_rounded_on_the_paths_domain():
 
 def test_distance_to_torch_log_on_this_host():
     """Not a parity claim, a measurement with a loose ceiling: on an AVX-512 host MKL's vsLn differs from the correctly rounded value
-    in ~5e-5 of the softmax probabilities (one ulp each); on an AVX2 host in ~7e-2.  The window fractions agree exactly on AVX-512."""
+    in ~5e-5 of the softmax probabilities (one ulp each); on its AVX2 path (AVX2 hosts, AMD hosts) in ~3e-2 to 7e-2.  The window fractions agree exactly on AVX-512."""
     lg = smooth_logits(19, 256, 512, 5)
     p = torch.softmax(lg, dim=0)
     q = (p + 1e-6)
     frac = bits_differ(ho.logf(q.numpy()), torch.log(q).numpy()) / q.numel()
     cap = torch.backends.cpu.get_cpu_capability()
-    print("torch.log vs correctly rounded logf: %.3e of the values differ (%s)" % (frac, cap))
-    if cap == "AVX512":
+    print("torch.log vs correctly rounded logf: %.3e of the values differ (%s, MKL AVX-512 path: %s)" % (frac, cap, mkl_log_is_avx512()))
+    if mkl_log_is_avx512():
         assert frac < 1e-3
         d = torch.tensor([n / c + 1e-6 for c in (4, 6, 9) for n in range(1, c + 1)], dtype=torch.float32)
         d = (torch.tensor([float(n) for c in (4, 6, 9) for n in range(1, c + 1)]) /
@@ -144,7 +156,7 @@ def test_pixel_entropy_chain_against_torch():
     ent = ho.uncertainty_from_probs(ho.softmax(lg.numpy()), "pixel_entropy", do_box=False)[0, 0]
     nd = bits_differ(ent, want)
     print("pixel entropy: %d of %d pixels differ from torch's" % (nd, ent.size))
-    if torch.backends.cpu.get_cpu_capability() == "AVX512":
+    if mkl_log_is_avx512():
         assert nd <= ent.size // 500
         assert np.abs(ent - want).max() <= 2.5e-7
 

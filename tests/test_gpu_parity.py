@@ -2395,6 +2395,58 @@ def test_bench_pool_images_and_branches_on_a_small_shape(dev):
             assert d["config"]["image_evaluations"] == 22 and d["steps"] == 6
 
 
+def test_bench_dump_outputs_are_the_last_timed_steps_and_repeat(dev, tmp_path):
+    """--dump-outputs DIR: finite float32 / float64 .npy files of what the LAST timed step computed -- its rows of the round's
+    pick tables, the scorer's map holding every pick's score at its position -- and two runs with the same arguments write the
+    same bytes.  --steps is the number of timed steps.  The bench's own check of the dumped map against the timed buffer must
+    also hold with half of each image already active (late_round: -inf there), on the hyper branch (the scorer's tail on its
+    own stream) with maps too large to keep whole (a strided sample), and from low-res sources."""
+    import glob
+    import json
+    from conftest import ROOT
+    H_, W_, B_, steps = 64, 128, 4, 3
+    got = []
+    for run in ("a", "b"):
+        r = _run_script([os.path.join(ROOT, "bench.py"), "--height", str(H_), "--width", str(W_), "--channels", "16", "--steps", str(steps),
+                         "--warmup", "1", "--batch", str(B_), "--ring", "8", "--cpu-images", "1",
+                         "--dump-outputs", str(tmp_path / run), "--dump-tables", str(tmp_path / (run + ".npz"))])
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == steps and d["config"]["image_evaluations"] == steps * B_ and d["ms_per_step"] > 0
+        assert d["parity_vs_cpu"] is True
+        files = {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(str(tmp_path / run / "*.npy"))}
+        assert sorted(files) == ["counts", "impurity", "picks", "sample_index", "score", "uncertainty"]
+        assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+        assert sum(v.nbytes for v in files.values()) <= 64 << 20
+        tab = np.load(str(tmp_path / (run + ".npz")))
+        assert np.array_equal(files["picks"], tab["tables"][-B_:]) and np.array_equal(files["counts"], tab["counts"][-B_:])
+        assert np.array_equal(files["sample_index"], np.arange(B_ * H_ * W_))          # small maps: kept whole
+        assert all(np.isfinite(v).all() for v in files.values())
+        score = files["score"].reshape(B_, H_, W_)
+        for i in range(B_):
+            n = int(files["counts"][i])
+            assert n == 10
+            rr, cc = files["picks"][i, :n, :2].astype(np.int64).T
+            assert np.array_equal(score[i, rr, cc].astype(np.float64), files["picks"][i, :n, 2])
+        got.append(files)
+    for k in got[0]:
+        assert got[0][k].tobytes() == got[1][k].tobytes(), k
+    for name, (h, w), extra in (("late", (H_, W_), ["--data", "late_round"]), ("hyper", (512, 1024), ["--branch", "hyper"]),
+                                ("lowres", (H_, W_), ["--source", "lowres"])):
+        r = _run_script([os.path.join(ROOT, "bench.py"), "--height", str(h), "--width", str(w), "--channels", "16", "--steps", "2",
+                         "--warmup", "1", "--batch", str(B_), "--ring", "8", "--cpu-images", "0", "--dump-outputs", str(tmp_path / name)]
+                        + extra)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert name != "hyper" or "own stream" in d["tail"]
+        files = {k: np.load(str(tmp_path / name / (k + ".npy"))) for k in ("score", "impurity", "uncertainty", "sample_index")}
+        assert all(np.isfinite(v).all() for v in files.values()), name
+        n = min(B_ * h * w, 1 << 20)
+        idx = files["sample_index"]
+        assert idx.shape == (n,) and (np.diff(idx) > 0).all() and idx[-1] < B_ * h * w, name
+        assert all(files[k].shape == (n,) for k in ("score", "impurity", "uncertainty")), name
+
+
 def test_head_kernel_variants_agree_bitwise(dev):
     """Round-2 kernels of the head tail against the round-1 kernels they replace (kept behind A/B switches) and the
     oracle: expmap0+project through an LDS tile (single read, hoisted exact division) vs the two-pass plane walk;
