@@ -10,6 +10,7 @@ import threading
 from . import _build
 
 F32, F64 = 0, 1
+I64, I32, U8 = 2, 3, 4                                              # HALO_I64 / HALO_I32 / HALO_U8: label and prediction maps
 UNC = {"entropy": 0, "pixel_entropy": 1, "oracle_acc": 2}          # everything else -> zeros (3)
 UNC_ZEROS = 3
 PUR = {"ripu": 0, "oracle_ripu": 1, "hyper": 2, "none": 3, "radius": 4, "euc_norm": 5}
@@ -66,6 +67,9 @@ SIGNATURES = {
     "halo_negative_learning_bwd": (_int, [_vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
     "halo_local_consistent_fwd": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "halo_local_consistent_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "halo_eval_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "halo_eval_confusion": (_int, [_vp, _i64, _int, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "halo_confusion_from_pred": (_int, [_vp, _int, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "halo_event_create": (_vp, []),
     "halo_event_record": (_int, [_vp, _vp]),
     "halo_event_elapsed_ms": (_int, [_vp, _vp, C.POINTER(C.c_float)]),
@@ -87,7 +91,7 @@ SIGNATURES = {
 
 # must equal HALO_ABI_VERSION of include/halo_hip.h; bumped whenever an exported signature changes, so a stale
 # library with the same symbol names but older argument lists is refused instead of being called with shifted arguments
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lock = threading.Lock()
 _handle = None
@@ -207,6 +211,15 @@ def dtype_code(t):
     if t.dtype == torch.float64:
         return F64
     raise TypeError("halo_amd: expected float32/float64 tensor, got %s" % t.dtype)
+
+
+def int_code(t):
+    """HALO_I64 / HALO_I32 / HALO_U8 of an integer map (labels, predictions)"""
+    import torch
+    code = {torch.int64: I64, torch.int32: I32, torch.uint8: U8}.get(t.dtype)
+    if code is None:
+        raise HaloUnsupported("halo_amd: expected an int64/int32/uint8 map, got %s" % t.dtype)
+    return code
 
 
 def require_device(*tensors):

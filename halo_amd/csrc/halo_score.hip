@@ -17,6 +17,7 @@
 #include "halo_common.hpp"
 #include "halo_devmath.hpp"
 #include "halo_select_plan.hpp"      // SelHdr / order_key: the score-range record handed to the selector
+#include "halo_softmax.hpp"           // Taps / make_taps, softmax_lean / softmax_general (shared with halo_eval.hip)
 #include <stdlib.h>
 
 namespace halo {
@@ -166,83 +167,7 @@ __device__ __forceinline__ void px_general(const float *__restrict__ lp, int O, 
     pred = pur_type == HALO_PUR_ORACLE_RIPU ? (g == 255 ? am : (int)g) : am;
 }
 
-__device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-// Lean softmax of NP pixels in registers.  Returns false -- p untouched -- when some lane of the wave needs the general
-// statement.  NaN logits hide from the two running extrema (a comparison with NaN is false), hence the sum t: it is NaN
-// iff a NaN (or both infinities) is among the classes; infinite logits make lo - m infinite or NaN.
-template <int O_T, int NP>
-__device__ __forceinline__ bool softmax_lean(float (&p)[NP][O_T])
-{
-    float m[NP], lo[NP], t[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) m[j] = lo[j] = t[j] = p[j][0];
-    // the two extrema through v_max3_f32 / v_min3_f32, two classes per instruction (a compare + select pair per class and
-    // extremum before: four 4-cycle instructions per class, now one).  They differ from the `>` / `<` scan only where it does
-    // not matter: a NaN operand is skipped (t is NaN then and the wave takes the general statement) and max(-0, +0) is +0
-    // (x - m is then +-0 either way and exp(+-0) = 1).
-#pragma unroll
-    for (int c = 1; c + 1 < O_T; c += 2) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            m[j] = vmax3(m[j], p[j][c], p[j][c + 1]);
-            lo[j] = vmin3(lo[j], p[j][c], p[j][c + 1]);
-            t[j] = (t[j] + p[j][c]) + p[j][c + 1];
-        }
-    }
-    if constexpr ((O_T - 1) % 2 == 1) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            m[j] = vmax3(m[j], p[j][O_T - 1], p[j][O_T - 1]);
-            lo[j] = vmin3(lo[j], p[j][O_T - 1], p[j][O_T - 1]);
-            t[j] = t[j] + p[j][O_T - 1];
-        }
-    }
-    bool general = false;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) general = general || !(lo[j] - m[j] >= -64.0f) || t[j] != t[j];
-    if (__any(general)) return false;
-    float s[NP], r[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) s[j] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < O_T; ++c) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) { p[j][c] = det_expf_core_small(p[j][c] - m[j]); s[j] = s[j] + p[j][c]; }
-    }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        r[j] = __builtin_amdgcn_rcpf(s[j]);
-        r[j] = __builtin_fmaf(__builtin_fmaf(-s[j], r[j], 1.0f), r[j], r[j]);
-    }
-#pragma unroll
-    for (int c = 0; c < O_T; ++c) {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            float q = p[j][c] * r[j];
-            q = __builtin_fmaf(__builtin_fmaf(-s[j], q, p[j][c]), r[j], q);
-            p[j][c] = __builtin_fmaf(__builtin_fmaf(-s[j], q, p[j][c]), r[j], q);
-        }
-    }
-    return true;
-}
-
-// General softmax in registers, for logits that exist nowhere in memory (the fused low-resolution path).
-template <int O_T, int NP>
-__device__ __forceinline__ void softmax_general(float (&p)[NP][O_T])
-{
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        float m = p[j][0], s = 0.0f;
-#pragma unroll
-        for (int c = 1; c < O_T; ++c) m = p[j][c] > m ? p[j][c] : m;
-#pragma unroll
-        for (int c = 0; c < O_T; ++c) { p[j][c] = det_expf(p[j][c] - m); s = s + p[j][c]; }
-#pragma unroll
-        for (int c = 0; c < O_T; ++c) p[j][c] = p[j][c] / s;
-    }
-}
+// (the register statements softmax_lean / softmax_general, with vmax3 / vmin3, are in halo_softmax.hpp)
 
 // From the probabilities of NP pixels: ent (per unc_type) and pred (per pur_type).  LEAN: p came from softmax_lean.
 template <int O_T, int NP, bool LEAN>
@@ -1195,22 +1120,8 @@ __global__ void __launch_bounds__(TPB) k_combine_box3(const TI *__restrict__ imp
 // that is written once and read once.  These kernels consume the LOW-RES tensors directly and
 // interpolate on the fly with exactly the arithmetic of k_bilinear (halo_hyperbolic.hip), so their
 // outputs are bit-identical to "upsample, then score" while the full-resolution tensor never exists.
+// The taps of one output coordinate (Taps / make_taps) are in halo_softmax.hpp.
 
-// bilinear taps of one output coordinate, weights in the tensor's dtype (align_corners=True)
-template <typename T> struct Taps { int i0, i1; T l0, l1; };
-template <typename T>
-__device__ __forceinline__ Taps<T> make_taps(int o, T scale, int in_size)
-{
-    Taps<T> t;
-    const T f = scale * (T)o;
-    int i0 = (int)f;
-    i0 = i0 > in_size - 1 ? in_size - 1 : i0;
-    t.i0 = i0;
-    t.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    t.l1 = f - (T)i0;
-    t.l0 = (T)1 - t.l1;
-    return t;
-}
 constexpr int LR_STAGE_IT = 3, LR_STAGE_G = 4;      // window elements per lane with precomputed offsets (<= 192 taps), channels per group
 constexpr int LR_TW = 64, LR_TH = 16, LR_PPT = 4;   // 64 x 16 output pixels per 256-thread block; a wave owns 4 consecutive rows x 64 columns
 

@@ -16,7 +16,7 @@
  *   - scratch comes from the caller: size it with the matching *_workspace_bytes()
  *   - return 0 on success, <0 on error (HALO_E_*); halo_last_error() gives the message of the
  *     calling thread's last failure
- *   - dtype codes: HALO_F32 = 0, HALO_F64 = 1
+ *   - dtype codes: HALO_F32 = 0, HALO_F64 = 1; integer maps (labels, predictions): HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4
  */
 #ifndef HALO_HIP_H
 #define HALO_HIP_H
@@ -28,9 +28,9 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 8
+#define HALO_ABI_VERSION 9
 
-enum { HALO_F32 = 0, HALO_F64 = 1 };
+enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4 };
 
 enum { HALO_OK = 0, HALO_E_ARG = -1, HALO_E_UNSUPPORTED = -2, HALO_E_WORKSPACE = -3, HALO_E_LAUNCH = -4 };
 
@@ -319,6 +319,26 @@ int halo_local_consistent_fwd(const float *x, const int64_t *label, int64_t B, i
                               size_t workspace_bytes, void *stream);
 int halo_local_consistent_bwd(const float *p, const float *coef_a, const float *coef_b, const uint8_t *mask, int64_t B, int64_t O,
                               int64_t h, int64_t w, const double *sums, const float *gloss, float *gx, void *stream);
+
+/* ---- validation metric (ABI 9): BaseLearner.inference + validation_step + intersectionAndUnionGPU
+ *  (core/train_learners.py:57-128, core/utils/misc.py:35-47) ----
+ *  halo_eval_confusion: logit holds `views` (1 or 2) low-resolution maps (K, h, w) f32 per image, view v of image i at
+ *    logit + (views*i + v) * logit_bstride (a head output of [x, flip(x)] for views = 2); label (B, H, W) of label_dtype
+ *    HALO_I64 / HALO_I32 / HALO_U8.  Per output pixel: bilinear upsampling to H x W (align_corners=True), softmax, view 1 read at
+ *    column W-1-x, (a + b) / 2, the first maximal class (a NaN counts as maximal) -- torch's CPU kernels bit for bit.
+ *    pred (B, H, W) i64 receives that arg-max when not NULL.
+ *  halo_confusion_from_pred: the same counting for a prediction map (B, H, W) of pred_dtype HALO_I64 / HALO_I32 / HALO_U8.
+ *  Both ADD the image's counts into counts (B, 3, K) i64, rows [intersection, union, target], with the reference's integer
+ *  semantics: o = (t == ignore_index) ? ignore_index : pred; output counts o, target counts t, intersection counts o where
+ *  o == t; each only where the value lies in [0, K) (torch.histc(bins=K, min=0, max=K-1)); union = output + target -
+ *  intersection.  K <= 1024; other K, views or dtypes return HALO_E_UNSUPPORTED.
+ *  workspace: halo_eval_workspace_bytes(B, K, H, W) (one u32 histogram of 3 x K per 1024 pixels). */
+size_t halo_eval_workspace_bytes(int64_t B, int64_t K, int64_t H, int64_t W);
+int halo_eval_confusion(const float *logit, int64_t logit_bstride, int views, int64_t K, int64_t h, int64_t w, const void *label,
+                        int label_dtype, int64_t H, int64_t W, int64_t B, int64_t ignore_index, int64_t *counts, int64_t *pred,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int halo_confusion_from_pred(const void *pred, int pred_dtype, const void *label, int label_dtype, int64_t K, int64_t H, int64_t W,
+                             int64_t B, int64_t ignore_index, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
