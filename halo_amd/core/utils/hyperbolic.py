@@ -13,7 +13,6 @@ device-side statement of the same formulas; bilinear_align_corners is inference-
 if a gradient is requested instead of silently detaching.
 """
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -202,14 +201,45 @@ def _pixel_contraction(D, X, chunk=512):
     return torch.bmm(Dk, Xk).sum(dim=0)
 
 
+def mlr_backward_terms(x, P, A, gout, c):
+    """HyperMLR backward through the term maps: one HIP kernel for the reverse sweep (halo_hypermlr_bwd_terms) + the two dense
+    contractions as library GEMMs (torch.einsum -> rocBLAS), W = [-P ; A/||A||], D = [dpx ; dxa].  Serves every shape; the
+    backward of _HyperMLRFn takes it where halo_hypermlr_backward does not serve the shape, and the tests use it as the
+    independent reference of that call.  x (B, C, H, W), P and A (O, C): float64, contiguous.  Returns (gx, gP, gA)."""
+    dev = x.device
+    B, Cc, H, W = x.shape
+    O, hw = P.shape[0], H * W
+    L = _lib.lib()
+    gout = gout.double().contiguous()
+    terms = torch.empty((5, B, O, hw), dtype=torch.float64, device=dev)       # dpx, dxa, dpp, dpa, dan
+    dxx = torch.empty((B, hw), dtype=torch.float64, device=dev)
+    nws = L.halo_hypermlr_workspace_bytes(O, Cc)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _lib.check(L.halo_hypermlr_bwd_terms(_lib.ptr(x), _lib.ptr(P), _lib.ptr(A), _lib.ptr(gout), B, Cc, O, hw,
+                                         float(c), _lib.ptr(terms[0]), _lib.ptr(terms[1]), _lib.ptr(dxx),
+                                         _lib.ptr(terms[2]), _lib.ptr(terms[3]), _lib.ptr(terms[4]), _lib.ptr(ws), nws,
+                                         _lib.stream_ptr(dev)), "halo_hypermlr_bwd_terms")
+    dpx, dxa = terms[0], terms[1]
+    dpp, dpa, dan = (terms[k].sum(dim=(0, 2)) for k in (2, 3, 4))            # (O,)
+    a_norm = A.norm(dim=1)                                                    # hyperbolic.py:172
+    dn = a_norm.clamp_min(1e-12)                                              # F.normalize eps, :173
+    An = A / dn[:, None]
+    xf = x.reshape(B, Cc, hw)
+    gx = torch.einsum("oc,bon->bcn", -P, dpx) + torch.einsum("oc,bon->bcn", An, dxa) + 2.0 * xf * dxx[:, None, :]
+    gW = _pixel_contraction(torch.cat([dpx, dxa], dim=1), xf)                 # (2O, C) = sum_{b,n} D[b,:,n] x[b,:,n]^T
+    g_negP = gW[:O]                                                           # d L / d (-P) through px
+    g_An = gW[O:] + dpa[:, None] * (-P)                                       # through xa and pa = <-P, An>
+    gP = -g_negP + dpp[:, None] * (2.0 * P) - dpa[:, None] * An               # pp = ||P||^2
+    gA = (g_An - (g_An * An).sum(dim=1, keepdim=True) * An) / dn[:, None] + dan[:, None] * A / a_norm[:, None]
+    return gx.reshape(B, Cc, H, W), gP, gA
+
+
 class _HyperMLRFn(torch.autograd.Function):
     """HyperMLR._hyper_logits (hyperbolic.py:120-184), float64, with gradients for x, P_MLR and A_MLR.
 
     backward, at the heads' shapes (<= 20 classes, 64 | C <= 256): ONE native call (halo_hypermlr_backward: the reverse sweep
     through the Moebius / projection / asinh algebra per pixel and class, d x = W^T D + 2 x dxx, d W = D x^T and the
-    parameter algebra: prep + three kernels, fixed summation order).  Any other shape (and HALO_MLR_BWD_TERMS=1, the cross-check):
-    one HIP kernel for the reverse sweep + the two dense contractions as library GEMMs (torch.einsum -> rocBLAS),
-        W = [-P ; A/||A||],  D = [dpx ; dxa]."""
+    parameter algebra: prep + three kernels, fixed summation order).  Any other shape: mlr_backward_terms."""
 
     @staticmethod
     def forward(ctx, x, P, A, c, out_dtype=torch.float64):
@@ -224,42 +254,22 @@ class _HyperMLRFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, P, A = ctx.saved_tensors
-        dev = x.device
         B, Cc, H, W = x.shape
         O, hw = P.shape[0], H * W
         L = _lib.lib()
-        nfused = 0 if os.environ.get("HALO_MLR_BWD_TERMS") else L.halo_hypermlr_backward_workspace_bytes(B, Cc, O, hw)
-        gout = (gout if (nfused and gout.dtype == torch.float32) else gout.double()).contiguous()
-        if nfused:
-            # the heads' shapes (<= 20 classes, 64 | C <= 256): the whole backward on the device in one call
-            gx = torch.empty((B, Cc, H, W), dtype=torch.float64, device=dev)
-            gP, gA = torch.empty_like(P), torch.empty_like(A)
-            ws = torch.empty(nfused, dtype=torch.uint8, device=dev)
-            _lib.check(L.halo_hypermlr_backward(_lib.ptr(x), _lib.ptr(P), _lib.ptr(A), _lib.ptr(gout), _lib.dtype_code(gout), B, Cc, O, hw, float(ctx.c),
-                                                _lib.ptr(gx), _lib.ptr(gP), _lib.ptr(gA), _lib.ptr(ws), nfused, _lib.stream_ptr(dev)),
-                       "halo_hypermlr_backward")
-            return gx, gP, gA, None, None
-        terms = torch.empty((5, B, O, hw), dtype=torch.float64, device=dev)       # dpx, dxa, dpp, dpa, dan
-        dxx = torch.empty((B, hw), dtype=torch.float64, device=dev)
-        nws = L.halo_hypermlr_workspace_bytes(O, Cc)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        _lib.check(L.halo_hypermlr_bwd_terms(_lib.ptr(x), _lib.ptr(P), _lib.ptr(A), _lib.ptr(gout), B, Cc, O, hw,
-                                             float(ctx.c), _lib.ptr(terms[0]), _lib.ptr(terms[1]), _lib.ptr(dxx),
-                                             _lib.ptr(terms[2]), _lib.ptr(terms[3]), _lib.ptr(terms[4]), _lib.ptr(ws), nws,
-                                             _lib.stream_ptr(dev)), "halo_hypermlr_bwd_terms")
-        dpx, dxa = terms[0], terms[1]
-        dpp, dpa, dan = (terms[k].sum(dim=(0, 2)) for k in (2, 3, 4))            # (O,)
-        a_norm = A.norm(dim=1)                                                    # hyperbolic.py:172
-        dn = a_norm.clamp_min(1e-12)                                              # F.normalize eps, :173
-        An = A / dn[:, None]
-        xf = x.reshape(B, Cc, hw)
-        gx = torch.einsum("oc,bon->bcn", -P, dpx) + torch.einsum("oc,bon->bcn", An, dxa) + 2.0 * xf * dxx[:, None, :]
-        gW = _pixel_contraction(torch.cat([dpx, dxa], dim=1), xf)                 # (2O, C) = sum_{b,n} D[b,:,n] x[b,:,n]^T
-        g_negP = gW[:O]                                                           # d L / d (-P) through px
-        g_An = gW[O:] + dpa[:, None] * (-P)                                       # through xa and pa = <-P, An>
-        gP = -g_negP + dpp[:, None] * (2.0 * P) - dpa[:, None] * An               # pp = ||P||^2
-        gA = (g_An - (g_An * An).sum(dim=1, keepdim=True) * An) / dn[:, None] + dan[:, None] * A / a_norm[:, None]
-        return gx.reshape(B, Cc, H, W), gP, gA, None, None
+        nfused = L.halo_hypermlr_backward_workspace_bytes(B, Cc, O, hw)
+        if not nfused:
+            return mlr_backward_terms(x, P, A, gout, ctx.c) + (None, None)
+        # the heads' shapes (<= 20 classes, 64 | C <= 256): the whole backward on the device in one call
+        dev = x.device
+        gout = (gout if gout.dtype == torch.float32 else gout.double()).contiguous()
+        gx = torch.empty((B, Cc, H, W), dtype=torch.float64, device=dev)
+        gP, gA = torch.empty_like(P), torch.empty_like(A)
+        ws = torch.empty(nfused, dtype=torch.uint8, device=dev)
+        _lib.check(L.halo_hypermlr_backward(_lib.ptr(x), _lib.ptr(P), _lib.ptr(A), _lib.ptr(gout), _lib.dtype_code(gout), B, Cc, O, hw, float(ctx.c),
+                                            _lib.ptr(gx), _lib.ptr(gP), _lib.ptr(gA), _lib.ptr(ws), nfused, _lib.stream_ptr(dev)),
+                   "halo_hypermlr_backward")
+        return gx, gP, gA, None, None
 
 
 class HyperMapper(object):

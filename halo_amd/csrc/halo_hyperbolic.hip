@@ -74,10 +74,10 @@ __device__ __forceinline__ double div_by(float x, double n, double r)
 
 constexpr int EXP_LD = 8;      // 16-byte loads in flight per lane while staging
 
-// A block walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... (one tile per block in the default launch) and requests the
-// first EXP_LD 16-byte groups per thread of its NEXT tile before it touches the current one, so that in a persistent launch
-// (HALO_EXPMAP_PERSISTENT=1) those loads are in flight during the serial part of a tile -- one lane per pixel running the
-// norm's fma chain over C channels while the other lanes of the block have nothing to do -- and during its write phase.
+// A block walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... (the host launches one block per tile) and requests the first
+// EXP_LD 16-byte groups per thread of its NEXT tile before it touches the current one, so that a block walking several tiles has
+// those loads in flight during the serial part of a tile -- one lane per pixel running the norm's fma chain over C channels while
+// the other lanes of the block have nothing to do -- and during its write phase.
 __global__ void __launch_bounds__(HTPB, 4) k_expmap0_project_tile(const float *__restrict__ x, double *__restrict__ y, long long outer,
                                                                int C, long long inner, int pshift, double ks, double rks,
                                                                double maxnorm)
@@ -1309,8 +1309,7 @@ __global__ void __launch_bounds__(HTPB) k_hypermlr_bwd_terms(const double *__res
 //                      matrix D, 2O x pixels) and dxx go to the workspace, the three per-class sums (dpp, dpa, d||A||) leave as one
 //                      partial per workgroup (fixed shuffle tree, fixed order afterwards: deterministic);
 //   k_mlr_bwd_dxw      gx = W^T D + 2 x dxx  and  d W = D x^T  in ONE pass over D and x on the f64 matrix cores, the tile transposed
-//                      through LDS between the two products; one (2O x C) partial of d W per persistent workgroup
-//                      (k_mlr_bwd_dx + k_mlr_bwd_weights: the same as two kernels, kept as the cross-check, HALO_MLR_BWD_DXW=0);
+//                      through LDS between the two products; one (2O x C) partial of d W per persistent workgroup;
 //   k_mlr_bwd_final    sums the partials in a fixed order and applies the (O,C)-sized algebra (||P||^2, <-P,A^>, F.normalize).
 // Serves O <= MLRB_OP classes and C a multiple of 64 up to 256 (the heads: 19 classes, 64 channels); anything else keeps the
 // term-map path above.
@@ -1428,185 +1427,17 @@ __global__ void __launch_bounds__(MLRB_TPB, SCALAR_W ? 3 : 2) k_mlr_bwd_pixels(c
     }
 }
 
-// d x = W^T D + 2 x dxx on the f64 matrix cores: out[channel][pixel] = sum_k W^T[channel][k] D[k][pixel], k over the 2O rows of D.
-// A operand (16 channels x 4 rows of D) = weights, constant over the launch: all of them sit in registers (KS x 4 doubles per lane);
-// B operand (4 rows of D x 16 pixels): lane (col = lane & 15, k = lane >> 4) loads D[4 ks + k][p0 + col] -- 128 contiguous bytes per
-// row; the result lane holds pixel (lane & 15) of channels (lane >> 4) + 4 q of each 16-channel tile, so x is read and d x written
-// in 128-byte row segments as well.  A wave walks 16-pixel tiles; blockIdx.y is the 64-channel block.
+// d x = W^T D + 2 x dxx  AND  d W = D x^T  in one pass over D and x on the f64 matrix cores (as two kernels they read x twice and D
+// three times between them, and were HBM-bound at large pixel counts).  d x: out[channel][pixel] = sum_k W^T[channel][k] D[k][pixel],
+// k over the 2O rows of D; the A operand (16 channels x 4 rows of D) is the weights, constant over the launch, the B operand (4 rows of
+// D x 16 pixels) comes from lane (pixel = lane & 15, k = lane >> 4), which loads D[4 ks + k][pixel] -- 128 contiguous bytes per row --
+// and x[16 ct + k + 4 q][pixel]; the result lane holds pixel (lane & 15) of channels (lane >> 4) + 4 q of each 16-channel tile, so x
+// is read and d x written in 128-byte row segments as well.  A wave walks 16-pixel tiles; blockIdx.y is the 64-channel block.  After
+// the d x MFMAs (weights from an LDS image) the wave parks D and x of the tile in its own LDS slab and reads them back TRANSPOSED for
+// the d W MFMAs, whose k slot is the pixel (the k slot of an MFMA is ANY pixel as long as both operands agree on it): lane (row =
+// lane & 15, slot = lane >> 4) takes D[16 rt + row][4 e + slot] and x[16 ct + row][4 e + slot].  48 x 64 d W accumulators stay in
+// registers over the wave's tiles.
 constexpr int MLRX_KS = (2 * MLRB_OP + 3) / 4;                           // k steps covering 2O <= 40 rows
-__global__ void __launch_bounds__(256) k_mlr_bwd_dx(const double *__restrict__ x, const double *__restrict__ consts, const double *__restrict__ Dws,
-                                                    const double *__restrict__ dxx, int O, int C, long long hw, int Bn, double *__restrict__ gx)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, k = lane >> 4, cb = blockIdx.y;
-    const double *An = consts + 3 * O, *nP = consts + 3 * O + (size_t)O * C;
-    double aw[MLRX_KS][4];
-#pragma unroll
-    for (int ks = 0; ks < MLRX_KS; ++ks) {
-        const int kk = 4 * ks + k;                                       // row of D: dpx of class kk (< O), dxa of class kk - O
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            const int c = cb * 64 + ct * 16 + col;
-            aw[ks][ct] = kk < O ? nP[(size_t)kk * C + c] : (kk < 2 * O ? An[(size_t)(kk - O) * C + c] : 0.0);
-        }
-    }
-    const long long tpi = (hw + 15) / 16, ntiles = tpi * Bn, tstride = (long long)gridDim.x * 4;
-    // the D operand of the wave's NEXT tile is requested before this tile's MFMAs (a tile's 40 MFMAs last about as long as an HBM
-    // round trip under load: unpipelined, two waves per SIMD left the matrix pipe idle half the time)
-    auto load_d = [&](long long t_, double (&d)[MLRX_KS]) {
-        const long long tl = t_ < ntiles ? t_ : ntiles - 1;
-        const int b = (int)(tl / tpi);
-        const long long p = (tl % tpi) * 16 + col, pc = p < hw ? p : hw - 1;
-#pragma unroll
-        for (int ks = 0; ks < MLRX_KS; ++ks) {
-            const int kk = 4 * ks + k;
-            // unconditional (the two padding rows of the last step read row 0) + select: under a lane condition this load is a
-            // branch region whose merge waits for EVERY load in flight -- the prefetch it belongs to included
-            const double v = Dws[((size_t)b * 2 * O + (kk < 2 * O ? kk : 0)) * hw + pc];
-            d[ks] = kk < 2 * O ? v : 0.0;
-        }
-    };
-    double bd[MLRX_KS], bn[MLRX_KS];
-    long long t_ = (long long)blockIdx.x * 4 + wave;
-    load_d(t_, bd);
-    for (; t_ < ntiles; t_ += tstride) {
-        const int b = (int)(t_ / tpi);
-        const long long p = (t_ % tpi) * 16 + col;
-        const bool in = p < hw;
-        const long long pc = in ? p : hw - 1;
-        load_d(t_ + tstride, bn);
-        const double two_dxx = 2.0 * dxx[(size_t)b * hw + pc];
-        double xv[4][4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xv[ct][q] = x[((size_t)b * C + cb * 64 + ct * 16 + k + 4 * q) * hw + pc];
-        v4d_t acc[4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[ct] = (v4d_t){0, 0, 0, 0};
-#pragma unroll
-        for (int ks = 0; ks < MLRX_KS; ++ks)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(aw[ks][ct], bd[ks], acc[ct], 0, 0, 0);
-        if (in)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    gx[((size_t)b * C + cb * 64 + ct * 16 + k + 4 * q) * hw + p] = __builtin_fma(two_dxx, xv[ct][q], acc[ct][q]);
-#pragma unroll
-        for (int ks = 0; ks < MLRX_KS; ++ks) bd[ks] = bn[ks];
-    }
-}
-
-// d W = D x^T on the f64 matrix cores (2O x C outputs, contraction over ALL pixels): a wave walks 16-pixel steps s, s + S, ...; in a
-// step lane (r = lane & 15, k = lane >> 4) loads pixels 4k .. 4k+3 of D rows r, 16 + r, 32 + r and of x rows r, 16 + r
-// (the two 16-column tiles of column block blockIdx.y) -- 32 contiguous bytes per lane, 128 per row -- and issues 4 x 6 v_mfma_f64_16x16x4_f64
-// (the k slot of an MFMA is ANY pixel as long as both operands agree on it).  48 x 32 accumulators stay in registers over the
-// wave's steps; the workgroup's four waves are added through LDS as (0 + 1) + (2 + 3) and leave ONE partial per workgroup and
-// column block.  (First version, VALU over LDS-staged chunks: 205 us at the training shape, latency-bound in its staging loop.)
-__global__ void __launch_bounds__(256) k_mlr_bwd_weights(const double *__restrict__ x, const double *__restrict__ Dws, int O, int C,
-                                                         long long hw, int Bn, int vec_ok, double *__restrict__ w_part)
-{
-    constexpr int NCT = 2;                                               // 16-column tiles per workgroup (blockIdx.y = 32-column block): 24 accumulators,
-    __shared__ double s_acc[2][48 * 16 * NCT];                           // several waves per SIMD to cover the operand loads
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, k = lane >> 4, cb = blockIdx.y;
-    const long long spi = (hw + 15) / 16, nsteps = spi * Bn;             // steps per image
-    const bool vec = vec_ok != 0;                                        // host: hw % 4 == 0 and 16-byte aligned bases -> aligned pixel quads
-    v4d_t acc[3][NCT];
-#pragma unroll
-    for (int rt = 0; rt < 3; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[rt][ct] = (v4d_t){0, 0, 0, 0};
-    auto load_ops = [&](long long s_, double (&av)[3][4], double (&bv)[NCT][4]) {
-        const long long sl = s_ < nsteps ? s_ : nsteps - 1;              // the look-ahead past the wave's last step re-reads it (never used)
-        const int b = (int)(sl / spi);
-        const long long p = (sl % spi) * 16 + 4 * k;
-#pragma unroll
-        for (int rt = 0; rt < 3; ++rt) {
-            const int j = rt * 16 + r;
-            const double *src = Dws + ((size_t)b * 2 * O + (j < 2 * O ? j : 0)) * hw + p;
-            if (vec && p < hw && j < 2 * O) {                            // (here the lane condition pays: unconditional loads of the 10 padding
-                const d2_h v0 = *reinterpret_cast<const d2_h *>(src), v1 = *reinterpret_cast<const d2_h *>(src + 2);      // rows + select measured 233 us against 185)
-                av[rt][0] = v0.x; av[rt][1] = v0.y; av[rt][2] = v1.x; av[rt][3] = v1.y;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) av[rt][e] = (j < 2 * O && p + e < hw) ? src[e] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const double *src = x + ((size_t)b * C + cb * (16 * NCT) + ct * 16 + r) * hw + p;
-            if (vec && p < hw) {
-                const d2_h v0 = *reinterpret_cast<const d2_h *>(src), v1 = *reinterpret_cast<const d2_h *>(src + 2);
-                bv[ct][0] = v0.x; bv[ct][1] = v0.y; bv[ct][2] = v1.x; bv[ct][3] = v1.y;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bv[ct][e] = p + e < hw ? src[e] : 0.0;      // a zero on either side drops the pixel
-            }
-        }
-    };
-    double av[3][4], bv[NCT][4], an_[3][4], bn_[NCT][4];
-    const long long sstride = (long long)gridDim.x * 4;
-    long long s_ = (long long)blockIdx.x * 4 + wave;
-    load_ops(s_, av, bv);
-    for (; s_ < nsteps; s_ += sstride) {
-        load_ops(s_ + sstride, an_, bn_);                                // the next step's operands travel during this step's 24 MFMAs
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int rt = 0; rt < 3; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt][e], bv[ct][e], acc[rt][ct], 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int rt = 0; rt < 3; ++rt) av[rt][e] = an_[rt][e];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) bv[ct][e] = bn_[ct][e];
-        }
-    }
-    // accumulator layout: lane holds column (lane & 15), rows (lane >> 4) + 4 q.  Waves 1 and 3 publish, 0 and 2 add; then 2 publishes, 0 adds.
-    auto publish = [&](double *dst) {
-#pragma unroll
-        for (int rt = 0; rt < 3; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) dst[(rt * 16 + k + 4 * q) * (16 * NCT) + ct * 16 + r] = acc[rt][ct][q];
-    };
-    auto absorb = [&](const double *src) {
-#pragma unroll
-        for (int rt = 0; rt < 3; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[rt][ct][q] += src[(rt * 16 + k + 4 * q) * (16 * NCT) + ct * 16 + r];
-    };
-    if (wave & 1) publish(s_acc[wave >> 1]);
-    __syncthreads();
-    if (!(wave & 1)) absorb(s_acc[wave >> 1]);
-    __syncthreads();
-    if (wave == 2) publish(s_acc[0]);
-    __syncthreads();
-    if (wave == 0) {
-        absorb(s_acc[0]);
-#pragma unroll
-        for (int rt = 0; rt < 3; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int j = rt * 16 + k + 4 * q;
-                    if (j < 2 * O) w_part[((size_t)blockIdx.x * 2 * O + j) * C + cb * (16 * NCT) + ct * 16 + r] = acc[rt][ct][q];
-                }
-    }
-}
-
-// d x AND d W in one pass over D and x (the two kernels above read x twice and D three times between them, and are HBM-bound at large
-// pixel counts).  A wave takes a 16-pixel tile in the d x kernel's layout -- lane (pixel = lane & 15, k = lane >> 4) holds D[4 ks + k][pixel]
-// and x[16 ct + k + 4 q][pixel] -- runs the d x MFMAs (weights from an LDS image), then parks D and x of the tile in its own LDS
-// slab and reads them back TRANSPOSED for the d W MFMAs, whose k slot is the pixel: lane (row = lane & 15, slot = lane >> 4) takes
-// D[16 rt + row][4 e + slot] and x[16 ct + row][4 e + slot].  48 x 64 d W accumulators stay in registers over the wave's tiles.
 constexpr int MLRZ_RS = 17, MLRZ_WS = 66;                                // row strides (doubles) of the per-wave slabs / of the weight image
 __global__ void __launch_bounds__(256, 2) k_mlr_bwd_dxw(const double *__restrict__ x, const double *__restrict__ consts, const double *__restrict__ Dws,
                                                         const double *__restrict__ dxx, int O, int C, long long hw, int Bn, double *__restrict__ gx,
@@ -1623,6 +1454,8 @@ __global__ void __launch_bounds__(256, 2) k_mlr_bwd_dxw(const double *__restrict
     }
     __syncthreads();
     const long long tpi = (hw + 15) / 16, ntiles = tpi * Bn, tstride = (long long)gridDim.x * 4;
+    // the D operand of the wave's NEXT tile is requested before this tile's MFMAs (a tile's 40 d x MFMAs last about as long as an HBM
+    // round trip under load: unpipelined, two waves per SIMD left the matrix pipe idle half the time)
     auto load_d = [&](long long t_, double (&d)[MLRX_KS]) {
         const long long tl = t_ < ntiles ? t_ : ntiles - 1;
         const int b = (int)(tl / tpi);
@@ -1630,7 +1463,9 @@ __global__ void __launch_bounds__(256, 2) k_mlr_bwd_dxw(const double *__restrict
 #pragma unroll
         for (int ks = 0; ks < MLRX_KS; ++ks) {
             const int kk = 4 * ks + k;
-            const double v = Dws[((size_t)b * 2 * O + (kk < 2 * O ? kk : 0)) * hw + pc];     // unconditional + select (see k_mlr_bwd_dx)
+            // unconditional (the two padding rows of the last step read row 0) + select: under a lane condition this load is a
+            // branch region whose merge waits for EVERY load in flight -- the prefetch it belongs to included
+            const double v = Dws[((size_t)b * 2 * O + (kk < 2 * O ? kk : 0)) * hw + pc];
             d[ks] = kk < 2 * O ? v : 0.0;
         }
     };
@@ -1800,6 +1635,11 @@ using namespace halo;
 
 static inline unsigned nblocks(long long n) { return (unsigned)cdiv(n, HTPB); }
 
+// Test hook, read at every launch of the one-quotient HyperMLR epilogue (halo_hypermlr_logits' resident kernel, halo_head_tail):
+// HALO_MLR_EPI_REF set = the reference-order epilogue for every logit, the independent reference that tests/test_gpu_parity.py,
+// tests/fuzz_head.py and tools/ab_mlr_epilogue.py compare the default against.  Not a user option.
+static inline int mlr_epi_ref() { return getenv("HALO_MLR_EPI_REF") != nullptr; }
+
 extern "C" int halo_expmap0_project(const void *x, int x_dtype, double *y, int64_t outer, int64_t C, int64_t inner, double c,
                                     void *stream)
 {
@@ -1811,20 +1651,16 @@ extern "C" int halo_expmap0_project(const void *x, int x_dtype, double *y, int64
     // that leaves P >= 32 (a full 128-byte line per channel row), up to 96 KiB otherwise
     int pshift = 0;
     size_t lds = 0;
-    if (x_dtype == HALO_F32 && inner >= 4 && inner % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
-        !getenv("HALO_EXPMAP_PLANES")) {                       // A/B switch: the two-pass kernel
+    if (x_dtype == HALO_F32 && inner >= 4 && inner % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0) {
         pshift = 8;                                             // P = 256
-        const char *ekb = getenv("HALO_EXPMAP_TILE_KB");                    // A/B switch: LDS bytes of a tile (default 32 KiB)
-        const size_t tile_cap = (size_t)(ekb ? atoi(ekb) : 32) * 1024;
-        while (pshift > 5 && ((size_t)C << pshift) * 4 > tile_cap) --pshift;
+        while (pshift > 5 && ((size_t)C << pshift) * 4 > 32 * 1024) --pshift;
         while (pshift > 2 && (1ll << (pshift - 1)) >= inner) --pshift;      // tiny planes: no wider than needed
         lds = ((size_t)C << pshift) * 4 + 3 * ((size_t)8 << pshift);
         if (lds > 96 * 1024) pshift = 0;
     }
-    // the head's channel counts (<= 64): every channel of a lane's pixel pair lives in registers -- no tile (HALO_EXPMAP_NOREGS=1:
-    // A/B switch, the LDS-tile kernel; same bits)
+    // the head's channel counts (<= 64): every channel of a lane's pixel pair lives in registers -- no tile
     if (x_dtype == HALO_F32 && C <= 64 && inner % 2 == 0 && inner < (1ll << 31) && outer <= 65535 && ((uintptr_t)x % 8) == 0 &&
-        ((uintptr_t)y % 16) == 0 && !getenv("HALO_EXPMAP_NOREGS") && !getenv("HALO_EXPMAP_PLANES")) {
+        ((uintptr_t)y % 16) == 0) {
         const dim3 gr((unsigned)cdiv(inner / 2, 64), (unsigned)outer);
 #define HALO_EXPR(CC_, EX_) hipLaunchKernelGGL((k_expmap0_project_regs<CC_, EX_>), gr, dim3(64), 0, st, (const float *)x, y, (long long)outer, (int)C, (long long)inner, ks, rks, maxnorm)
         if (C <= 16) HALO_EXPR(16, false);
@@ -1837,13 +1673,10 @@ extern "C" int halo_expmap0_project(const void *x, int x_dtype, double *y, int64
         if (lds > 64 * 1024 && !raise_lds_limit(seen, (const void *)k_expmap0_project_tile, 96 * 1024))
             return fail(HALO_E_LAUNCH, "halo_expmap0_project: cannot raise the dynamic LDS limit");
         const long long tiles = (inner + (1ll << pshift) - 1) >> pshift, ntiles = outer * tiles;
-        // One block per tile.  HALO_EXPMAP_PERSISTENT=1 launches only as many blocks as the CUs hold and lets each walk its
-        // tiles with the next tile's loads in flight (round-3 experiment: no gain at these sizes -- 0.096 vs 0.098 ms at
-        // C=256 256x512, 0.136 vs 0.122 ms at C=64 640x1280: the whole kernel is ~100 us, a block sees only 4 tiles)
-        long long resident = 256ll * (long long)((160 * 1024) / (lds + 256) > 8 ? 8 : (160 * 1024) / (lds + 256));
-        if (resident < 256) resident = 256;
-        const long long nblk = (getenv("HALO_EXPMAP_PERSISTENT") && ntiles > resident) ? resident : ntiles;
-        hipLaunchKernelGGL(k_expmap0_project_tile, dim3((unsigned)nblk), dim3(HTPB), lds, st, (const float *)x, y,
+        // One block per tile (round 3: a persistent launch, as many blocks as the CUs hold, each walking its tiles with the next
+        // tile's loads in flight, gained nothing at these sizes -- 0.096 vs 0.098 ms at C=256 256x512, 0.136 vs 0.122 ms at C=64
+        // 640x1280: the whole kernel is ~100 us, a block sees only 4 tiles)
+        hipLaunchKernelGGL(k_expmap0_project_tile, dim3((unsigned)ntiles), dim3(HTPB), lds, st, (const float *)x, y,
                            (long long)outer, (int)C, (long long)inner, pshift, ks, rks, maxnorm);
     }
     else if (x_dtype == HALO_F32)
@@ -1906,7 +1739,7 @@ extern "C" int halo_hypermlr_logits(const double *x, const double *P, const doub
     // matrix-core path: up to 32 classes (two 16-column tiles per operand); anything else takes the VALU kernel
     if (out_dtype != HALO_F32 && out_dtype != HALO_F64) return fail(HALO_E_ARG, "halo_hypermlr_logits: bad out dtype");
     // weights-resident matrix-core kernel when the [-P | A^] image plus the per-wave staging fits LDS
-    if (O <= 32 && getenv("HALO_MLR_VALU") == nullptr && getenv("HALO_MLR_CHUNKED") == nullptr) {
+    if (O <= 32) {
         const int NT = O <= 16 ? 2 : (O <= 24 ? 3 : 4);
         const int wstride = (int)C + (int)(((2 - C) % 32 + 32) % 32);            // (C + pad) mod 32 == 2
         const size_t lds = ((size_t)2 * O * wstride + (size_t)(MLRP_TPB / 64) * (2 * O * 32 + 32)) * 8;
@@ -1915,7 +1748,7 @@ extern "C" int halo_hypermlr_logits(const double *x, const double *P, const doub
             const long long tiles_per_img = cdiv(hw, 32), ntiles = tiles_per_img * B;
             long long gx = cdiv(ntiles, MLRP_TPB / 64);
             gx = gx > 256 ? 256 : gx;                                              // one resident workgroup per CU, persistent over tiles
-            const int force_ref = getenv("HALO_MLR_EPI_REF") != nullptr;        // A/B and test switch: the reference-order epilogue for every logit
+            const int force_ref = mlr_epi_ref();
 #define HALO_MLRP(T, NT_)                                                                                                          \
     {                                                                                                                             \
         static LdsLimitSeen seen;                                                                                                 \
@@ -1930,7 +1763,8 @@ extern "C" int halo_hypermlr_logits(const double *x, const double *P, const doub
             return check_launch("halo_hypermlr_logits");
         }
     }
-    if (O <= 32 && getenv("HALO_MLR_VALU") == nullptr) {
+    // the chunked matrix-core kernel: a C the resident kernel's stage ring does not divide, an odd pixel count, unaligned x
+    if (O <= 32) {
         dim3 gridm((unsigned)cdiv(hw, (HTPB / 64) * MLR_MT * 16), (unsigned)B);
 #define HALO_MLR(T, NT_) hipLaunchKernelGGL((k_hypermlr_mfma<T, NT_>), gridm, dim3(HTPB), 0, st, x, (const double *)consts, (int)O, (int)C, (long long)hw, c, (T *)out)
         if (out_dtype == HALO_F32) { if (O <= 16) HALO_MLR(float, 2); else if (O <= 24) HALO_MLR(float, 3); else HALO_MLR(float, 4); }
@@ -1959,8 +1793,8 @@ extern "C" int halo_head_tail(const float *feat, const double *P, const double *
     if (c <= 0) return fail(HALO_E_UNSUPPORTED, "halo_head_tail: curvature must be > 0");
     if (out_dtype != HALO_F32 && out_dtype != HALO_F64) return fail(HALO_E_ARG, "halo_head_tail: bad out dtype");
     if (!workspace || workspace_bytes < halo_hypermlr_workspace_bytes(O, C)) return fail(HALO_E_WORKSPACE, "halo_head_tail: workspace too small");
-    if (C != HT_C || O > 32 || hw % 2 != 0 || hw < 2 || ((uintptr_t)feat % 8) != 0 || ((uintptr_t)embed % 16) != 0 || getenv("HALO_HEAD_TAIL_SPLIT"))
-        return 1;                                                                 // (the variable: A/B and test switch)
+    if (C != HT_C || O > 32 || hw % 2 != 0 || hw < 2 || ((uintptr_t)feat % 8) != 0 || ((uintptr_t)embed % 16) != 0)
+        return 1;
     hipStream_t st = (hipStream_t)stream;
     double *consts = (double *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     const int NT = O <= 16 ? 2 : (O <= 24 ? 3 : 4);
@@ -1974,7 +1808,7 @@ extern "C" int halo_head_tail(const float *feat, const double *P, const double *
     const long long tiles_per_img = cdiv(hw, 32), ntiles = tiles_per_img * B;
     long long gx = cdiv(ntiles, MLRP_TPB / 64);
     gx = gx > 256 ? 256 : gx;
-    const int force_ref = getenv("HALO_MLR_EPI_REF") != nullptr;
+    const int force_ref = mlr_epi_ref();
 #define HALO_HT(T, NT_)                                                                                                            \
     {                                                                                                                             \
         static LdsLimitSeen seen;                                                                                                 \
@@ -2190,34 +2024,33 @@ static void launch_bilinear_rows(const void *src, void *dst, int64_t planes, int
     if (gz > 65535) gz = 65535;
     // source columns one block can touch: its 256*VEC outputs span sw*(256*VEC-1) source units, plus the +1 taps
     const int64_t span = (int64_t)((double)sw * (double)(HTPB * VEC - 1)) + 4;
-    // BL_RO output rows per block where they touch at most BL_SR source rows (up-sampling by >= 0.8); HALO_BILINEAR_LDS1=1
-    // keeps the one-row kernel (A/B switch, same bits)
+    // BL_RO output rows per block where they touch at most BL_SR source rows (up-sampling by >= 0.8)
     const int64_t srows = (int64_t)((double)sh * (double)(BL_RO - 1)) + 3;
     // planes per chunk: BL_PCR where their taps fit 24 KiB of LDS (the x4 geometries: 6-7 blocks per CU), fewer for wide source
-    // windows (x1.6: 10 KiB per plane -> 2 planes) so that as many blocks stay resident; HALO_BILINEAR_PCR overrides (tuning aid)
+    // windows (x1.6: 10 KiB per plane -> 2 planes) so that as many blocks stay resident
     int pcr = BL_PCR;
     while (pcr > 1 && (size_t)pcr * srows * span * sizeof(T) > 24 * 1024) pcr >>= 1;
-    if (const char *e = getenv("HALO_BILINEAR_PCR")) { const int v = atoi(e); if (v >= 1 && v <= BL_PCR) pcr = v; }
     const size_t lds_r = (size_t)pcr * srows * span * sizeof(T);
     // (float32 with 4 pixels per lane stays on the one-row kernel: on the four-row kernel it needs 178 registers -- two blocks per CU --
     // and measured no faster at the v2 head's 640x1280 -> 1024x2048, 0.066 against 0.069 ms, and slower at x4: 0.044 against 0.039)
-    if (!(sizeof(T) == 4 && VEC == 4) && srows <= BL_SR && lds_r <= 48 * 1024 && cdiv(H, BL_RO) <= 65535 && !getenv("HALO_BILINEAR_ROWS") &&
-        !getenv("HALO_BILINEAR_LDS1")) {
-        const unsigned gyr = (unsigned)cdiv(H, BL_RO);
-        int64_t gzl = cdiv(8192, (int64_t)gx * gyr);
-        const int64_t chunks = cdiv(planes, pcr);
-        gzl = gzl < 1 ? 1 : (gzl > chunks ? chunks : gzl);
-        if (gzl > 65535) gzl = 65535;
-        hipLaunchKernelGGL((k_bilinear_lds_rows<T, VEC>), dim3(gx, gyr, (unsigned)gzl), dim3(HTPB), lds_r, st, (const T *)src, (T *)dst,
-                           (int)planes, (int)h, (int)w, (int)H, (int)W, sh, sw, (int)span, pcr);
-        return;
+    if constexpr (!(sizeof(T) == 4 && VEC == 4)) {
+        if (srows <= BL_SR && lds_r <= 48 * 1024 && cdiv(H, BL_RO) <= 65535) {
+            const unsigned gyr = (unsigned)cdiv(H, BL_RO);
+            int64_t gzl = cdiv(8192, (int64_t)gx * gyr);
+            const int64_t chunks = cdiv(planes, pcr);
+            gzl = gzl < 1 ? 1 : (gzl > chunks ? chunks : gzl);
+            if (gzl > 65535) gzl = 65535;
+            hipLaunchKernelGGL((k_bilinear_lds_rows<T, VEC>), dim3(gx, gyr, (unsigned)gzl), dim3(HTPB), lds_r, st, (const T *)src, (T *)dst,
+                               (int)planes, (int)h, (int)w, (int)H, (int)W, sh, sw, (int)span, pcr);
+            return;
+        }
     }
     const size_t lds = (size_t)BL_PC * 2 * span * sizeof(T);
     // float32 planes magnified >= 3x: the taps of a row come from a few hundred bytes that stay in the vector cache -- gathering them
     // from global memory measured FASTER than staging them (19 planes: 256x512 -> 1024x2048 29.9 against 35.2 us, 160x320 -> 640x1280
-    // 16.9 against 21.0; at x1.6 the staged kernel wins, 66 against 73).  HALO_BILINEAR_NOGATHER=1: A/B switch
-    const bool gather = sizeof(T) == 4 && (double)sw <= 1.0 / 3.0 && (double)sh <= 1.0 / 3.0 && !getenv("HALO_BILINEAR_NOGATHER");
-    if (lds <= 32 * 1024 && !getenv("HALO_BILINEAR_ROWS") && !gather) {      // A/B switch: taps gathered from global memory
+    // 16.9 against 21.0; at x1.6 the staged kernel wins, 66 against 73)
+    const bool gather = sizeof(T) == 4 && (double)sw <= 1.0 / 3.0 && (double)sh <= 1.0 / 3.0;
+    if (lds <= 32 * 1024 && !gather) {
         int64_t gzl = cdiv(8192, (int64_t)gx * H);
         const int64_t chunks = cdiv(planes, BL_PC);
         gzl = gzl < 1 ? 1 : (gzl > chunks ? chunks : gzl);
@@ -2236,7 +2069,7 @@ extern "C" int halo_bilinear_upsample(const void *src, void *dst, int dtype, int
     if (!src || !dst || planes <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return fail(HALO_E_ARG, "halo_bilinear_upsample: null/empty argument");
     if (dtype != HALO_F64 && dtype != HALO_F32) return fail(HALO_E_ARG, "halo_bilinear_upsample: bad dtype");
     hipStream_t st = (hipStream_t)stream;
-    const bool rows = H <= 65535 && planes <= 0x7fffffff && !getenv("HALO_BILINEAR_FLAT");     // A/B switch: one element per thread
+    const bool rows = H <= 65535 && planes <= 0x7fffffff;     // otherwise one element per thread (k_bilinear)
     const bool a16 = ((uintptr_t)dst % 16) == 0;
     if (rows && dtype == HALO_F64) {
         if (W % 2 == 0 && a16) launch_bilinear_rows<double, 2>(src, dst, planes, h, w, H, W, st);
@@ -2244,9 +2077,9 @@ extern "C" int halo_bilinear_upsample(const void *src, void *dst, int dtype, int
     } else if (rows) {
         // mild magnification (below x3: the v2 head's 640x1280 -> 1024x2048): two pixels per lane on the four-row kernel -- a source row
         // is staged once per four output rows; the one-row kernel that serves float32 x 4 stages two source rows for EVERY output row,
-        // 3.2x the input at x1.6 (HALO_BILINEAR_F32V4=1: A/B switch)
+        // 3.2x the input at x1.6
         const bool mild = H > 1 && W > 1 && (double)(h - 1) / (double)(H - 1) > 1.0 / 3.0 && (double)(w - 1) / (double)(W - 1) > 1.0 / 3.0;
-        if (W % 4 == 0 && a16 && !(mild && !getenv("HALO_BILINEAR_F32V4"))) launch_bilinear_rows<float, 4>(src, dst, planes, h, w, H, W, st);
+        if (W % 4 == 0 && a16 && !mild) launch_bilinear_rows<float, 4>(src, dst, planes, h, w, H, W, st);
         else if (W % 2 == 0 && ((uintptr_t)dst % 8) == 0) launch_bilinear_rows<float, 2>(src, dst, planes, h, w, H, W, st);
         else launch_bilinear_rows<float, 1>(src, dst, planes, h, w, H, W, st);
     } else {
@@ -2277,7 +2110,7 @@ extern "C" int halo_expmap0_project_bwd(const void *x, int x_dtype, const double
     return check_launch("halo_expmap0_project_bwd");
 }
 
-// ---- fused HyperMLR backward (k_mlr_bwd_pixels / _dx / _weights / _final).  Workspace: consts | D (B,2O,hw) | dxx (B,hw) | Wt (C,40) | class partials | weight partials.
+// ---- fused HyperMLR backward (k_mlr_bwd_pixels / _dxw / _final).  Workspace: consts | D (B,2O,hw) | dxx (B,hw) | Wt (C,40) | class partials | weight partials.
 static inline bool mlr_bwd_fused_ok(int64_t C, int64_t O) { return O >= 1 && O <= MLRB_OP && C % 64 == 0 && C >= 64 && C <= 256; }
 static inline int64_t mlr_bwd_pix_blocks(int64_t B, int64_t hw) { return cdiv(hw, MLRB_TPB) * B; }
 extern "C" size_t halo_hypermlr_backward_workspace_bytes(int64_t B, int64_t C, int64_t O, int64_t hw)
@@ -2313,9 +2146,8 @@ extern "C" int halo_hypermlr_backward(const double *x, const double *P, const do
     hipLaunchKernelGGL(k_mlr_prep, dim3((unsigned)O), dim3(64), (size_t)2 * C * sizeof(double), st, P, A, (int)O, (int)C, consts, Wt, MLRB_OP);
     {
         const dim3 gp((unsigned)cdiv(hw, MLRB_TPB), (unsigned)B);
-        // >= 2 resident waves on every SIMD: weights through the scalar cache (HALO_MLR_BWD_W=lds|scalar forces an arm: tests, A/B)
-        const char *wenv = getenv("HALO_MLR_BWD_W");
-        const bool scalar_w = wenv ? wenv[0] == 's' : (long long)B * hw >= 400000;
+        // >= 2 resident waves on every SIMD: weights through the scalar cache, otherwise from an LDS image (same bits)
+        const bool scalar_w = (long long)B * hw >= 400000;
 #define HALO_MLRB_PIX(SW_, TG_, LDS_)                                                                                              \
     hipLaunchKernelGGL((k_mlr_bwd_pixels<SW_, TG_>), gp, dim3(MLRB_TPB), LDS_, st, x, (const double *)consts, (const double *)Wt, (const TG_ *)gout, \
                        (int)O, (int)C, (long long)hw, c, Dws, dxx, cls_part)
@@ -2330,30 +2162,16 @@ extern "C" int halo_hypermlr_backward(const double *x, const double *P, const do
             if (gout_dtype == HALO_F32) HALO_MLRB_PIX(false, float, lds); else HALO_MLRB_PIX(false, double, lds);
         }
 #undef HALO_MLRB_PIX
+        // one pass for d x and d W (k_mlr_bwd_dxw): 2 x 64 x 160 x 320 123 us against 138 for the whole backward as two kernels,
+        // 1 x 64 x 640 x 1280 607 against 736
         const long long ntiles = cdiv(hw, 16) * B;
-        // one pass for d x and d W (k_mlr_bwd_dxw): 2 x 64 x 160 x 320 123 us against 138 for the whole backward, 1 x 64 x 640 x 1280 607 against
-        // 736.  HALO_MLR_BWD_DXW=0: the two separate kernels (the test's cross-check: identical d x, d W within 1e-12)
-        const char *fenv = getenv("HALO_MLR_BWD_DXW");
-        const bool one_pass = !(fenv && fenv[0] == '0');
-        unsigned g = 0;
-        if (one_pass) {
-            g = (unsigned)(cdiv(ntiles, 4) < MLRB_NWG ? cdiv(ntiles, 4) : MLRB_NWG);
-            const size_t lds = ((size_t)4 * MLRX_KS * MLRZ_WS + (size_t)4 * (4 * MLRX_KS + 64) * MLRZ_RS) * sizeof(double);
-            static LdsLimitSeen seen;
-            if (!raise_lds_limit(seen, (const void *)k_mlr_bwd_dxw, 96 * 1024))
-                return fail(HALO_E_LAUNCH, "halo_hypermlr_backward: cannot raise the dynamic LDS limit");
-            hipLaunchKernelGGL(k_mlr_bwd_dxw, dim3(g, (unsigned)(C / 64)), dim3(256), lds, st, x, (const double *)consts, (const double *)Dws, (const double *)dxx,
-                               (int)O, (int)C, (long long)hw, (int)B, gx, w_part);
-        } else {
-        const unsigned gdx = (unsigned)(cdiv(ntiles, 4) < 512 ? cdiv(ntiles, 4) : 512);
-        hipLaunchKernelGGL(k_mlr_bwd_dx, dim3(gdx, (unsigned)(C / 64)), dim3(256), 0, st, x, (const double *)consts, (const double *)Dws, (const double *)dxx,
-                           (int)O, (int)C, (long long)hw, (int)B, gx);
-        const long long nsteps = cdiv(hw, 16) * B;
-        g = (unsigned)(cdiv(nsteps, 4) < MLRB_NWG ? cdiv(nsteps, 4) : MLRB_NWG);
-        const int vec_ok = hw % 4 == 0 && (((uintptr_t)x | (uintptr_t)Dws) % 16) == 0;
-        hipLaunchKernelGGL(k_mlr_bwd_weights, dim3(g, (unsigned)(C / 32)), dim3(256), 0, st, x, (const double *)Dws, (int)O, (int)C, (long long)hw,
-                           (int)B, vec_ok, w_part);
-        }
+        const unsigned g = (unsigned)(cdiv(ntiles, 4) < MLRB_NWG ? cdiv(ntiles, 4) : MLRB_NWG);
+        const size_t lds = ((size_t)4 * MLRX_KS * MLRZ_WS + (size_t)4 * (4 * MLRX_KS + 64) * MLRZ_RS) * sizeof(double);
+        static LdsLimitSeen seen;
+        if (!raise_lds_limit(seen, (const void *)k_mlr_bwd_dxw, 96 * 1024))
+            return fail(HALO_E_LAUNCH, "halo_hypermlr_backward: cannot raise the dynamic LDS limit");
+        hipLaunchKernelGGL(k_mlr_bwd_dxw, dim3(g, (unsigned)(C / 64)), dim3(256), lds, st, x, (const double *)consts, (const double *)Dws, (const double *)dxx,
+                           (int)O, (int)C, (long long)hw, (int)B, gx, w_part);
         hipLaunchKernelGGL(k_mlr_bwd_final, dim3((unsigned)O), dim3(MLRF_TPB), 0, st, A, (const double *)consts, (const double *)w_part, (int)g,
                            (const double *)cls_part, (int)npb, (int)O, (int)C, gP, gA);
     }

@@ -443,7 +443,7 @@ extern "C" int halo_local_consistent_fwd(const float *x, const int64_t *label, i
         return fail(HALO_E_ARG, "halo_local_consistent_fwd: coef_a, coef_b and mask go together");
     const long long hw = (long long)h * w;
     const int nb = (int)cdiv(hw, LTPB);
-    const bool strip = getenv("HALO_LCL_PLAIN") == nullptr && B <= 65535 && cdiv(h, LCL_ROWS) <= 65535;      // A/B switch: the one-pixel-per-thread forward
+    const bool strip = B <= 65535 && cdiv(h, LCL_ROWS) <= 65535;      // otherwise the one-pixel-per-thread forward (grid limits)
     const dim3 gs((unsigned)cdiv(w, LTPB), (unsigned)cdiv(h, LCL_ROWS), (unsigned)B);
     const int nblk = strip ? (int)(gs.x * gs.y * gs.z) : nb * (int)B;
     if (!workspace || workspace_bytes < (size_t)nblk * 16 + 256) return fail(HALO_E_WORKSPACE, "halo_local_consistent_fwd: workspace too small");

@@ -637,7 +637,7 @@ template <typename TL>
 static int launch_region_impurity(const TL *pred, int64_t B, int64_t H, int64_t W, int k, float logK, float *imp, float *count,
                                   hipStream_t st, double *partials = nullptr, int pad = HALO_PAD_ZEROS)
 {
-    if (pad == HALO_PAD_ZEROS && k == 3 && cdiv(H, RI_TH) <= 65535 && B <= 65535 && !getenv("HALO_IMPURITY_GENERIC")) {     // A/B switch
+    if (pad == HALO_PAD_ZEROS && k == 3 && cdiv(H, RI_TH) <= 65535 && B <= 65535) {
         const dim3 grid((unsigned)cdiv(W, RI_TW), (unsigned)cdiv(H, RI_TH), (unsigned)B);
         hipLaunchKernelGGL((k_region_impurity3<TL>), grid, dim3(TPB), 0, st, pred, (int)H, (int)W, logK, imp, count, partials);
         return partials ? (int)(grid.x * grid.y) : 0;
@@ -924,10 +924,9 @@ __global__ void __launch_bounds__(TPB) k_combine(const TI *__restrict__ imp_raw,
 // writes: lo = 0, scale = NB1 -- exactly what k_sel_hist1 would count from the stored map (same coarse_bin, same exclusions).
 constexpr int CB_ROWS = 16;        // at most; fewer when the launch would otherwise not fill the chip (one image at a time)
 
-// NTS: the impurity / uncertainty maps are stored non-temporally (nothing on the device reads them again) and the raw impurity is
-// loaded non-temporally (read exactly once); the score map -- the selector's input -- and the entropy rows (shared with the
-// neighbouring workgroups) keep the default policy.
-template <typename TI, bool NTS>
+// Non-temporal impurity / uncertainty stores (nothing on the device reads them again) measured SLOWER: 233 against 214 us per
+// 16 images (NOTES.md, round 5); every access keeps the default policy.
+template <typename TI>
 __global__ void __launch_bounds__(TPB) k_combine_box3(const TI *__restrict__ imp_raw, const float *__restrict__ ent,
                                                       const double *__restrict__ stats, const unsigned char *__restrict__ active,
                                                       int H, int W, int pk, int normalize, TI *__restrict__ score,
@@ -1010,16 +1009,10 @@ __global__ void __launch_bounds__(TPB) k_combine_box3(const TI *__restrict__ imp
         if (!live || yy >= yend) return t;
         const size_t o = (size_t)b * hw + (size_t)yy * W + x;
         if constexpr (sizeof(TI) == 8) {
-            if constexpr (NTS) {
-                t.d0 = __builtin_nontemporal_load(reinterpret_cast<const cb_d2 *>(imp_raw + o));
-                t.d1 = __builtin_nontemporal_load(reinterpret_cast<const cb_d2 *>(imp_raw + o + 2));
-            } else {
-                t.d0 = *reinterpret_cast<const cb_d2 *>(imp_raw + o);
-                t.d1 = *reinterpret_cast<const cb_d2 *>(imp_raw + o + 2);
-            }
+            t.d0 = *reinterpret_cast<const cb_d2 *>(imp_raw + o);
+            t.d1 = *reinterpret_cast<const cb_d2 *>(imp_raw + o + 2);
         } else {
-            if constexpr (NTS) t.f = __builtin_nontemporal_load(reinterpret_cast<const cb_f4 *>(imp_raw + o));
-            else t.f = *reinterpret_cast<const cb_f4 *>(imp_raw + o);
+            t.f = *reinterpret_cast<const cb_f4 *>(imp_raw + o);
         }
         if (active) t.am = *reinterpret_cast<const unsigned *>(active + o);
         return t;
@@ -1085,25 +1078,14 @@ __global__ void __launch_bounds__(TPB) k_combine_box3(const TI *__restrict__ imp
             *reinterpret_cast<double2 *>(score + o) = make_double2(sc[0], sc[1]);
             *reinterpret_cast<double2 *>(score + o + 2) = make_double2(sc[2], sc[3]);
             if (imp_out) {
-                if constexpr (NTS) {
-                    __builtin_nontemporal_store((cb_d2){im[0], im[1]}, reinterpret_cast<cb_d2 *>(imp_out + o));
-                    __builtin_nontemporal_store((cb_d2){im[2], im[3]}, reinterpret_cast<cb_d2 *>(imp_out + o + 2));
-                } else {
-                    *reinterpret_cast<double2 *>(imp_out + o) = make_double2(im[0], im[1]);
-                    *reinterpret_cast<double2 *>(imp_out + o + 2) = make_double2(im[2], im[3]);
-                }
+                *reinterpret_cast<double2 *>(imp_out + o) = make_double2(im[0], im[1]);
+                *reinterpret_cast<double2 *>(imp_out + o + 2) = make_double2(im[2], im[3]);
             }
         } else {
             *reinterpret_cast<float4 *>(score + o) = make_float4(sc[0], sc[1], sc[2], sc[3]);
-            if (imp_out) {
-                if constexpr (NTS) __builtin_nontemporal_store((cb_f4){im[0], im[1], im[2], im[3]}, reinterpret_cast<cb_f4 *>(imp_out + o));
-                else *reinterpret_cast<float4 *>(imp_out + o) = make_float4(im[0], im[1], im[2], im[3]);
-            }
+            if (imp_out) *reinterpret_cast<float4 *>(imp_out + o) = make_float4(im[0], im[1], im[2], im[3]);
         }
-        if (unc_out) {
-            if constexpr (NTS) __builtin_nontemporal_store((cb_f4){un[0], un[1], un[2], un[3]}, reinterpret_cast<cb_f4 *>(unc_out + o));
-            else *reinterpret_cast<float4 *>(unc_out + o) = make_float4(un[0], un[1], un[2], un[3]);
-        }
+        if (unc_out) *reinterpret_cast<float4 *>(unc_out + o) = make_float4(un[0], un[1], un[2], un[3]);
     }
     if (count) {
         __syncthreads();
@@ -1914,7 +1896,7 @@ __global__ void __launch_bounds__(TPB) k_gram_lr(const double *__restrict__ feat
 // column the next lane's first (full-wave DPP shift); only lane 63 loads its right neighbour itself (8 bytes per row and
 // channel, clamped at the row's end).  Half the load instructions per byte of k_gram_lr, no idle 64th lane, and 512-column rows
 // split into four full waves.  Same fma chains, same bits.
-template <int UCH, bool NT, int R>
+template <int UCH, int R>
 __global__ void __launch_bounds__(TPB) k_gram_lr2(const double *__restrict__ feat, long long bstride, int C, int h, int w,
                                                   double *__restrict__ gram)
 {
@@ -1964,12 +1946,9 @@ __global__ void __launch_bounds__(TPB) k_gram_lr2(const double *__restrict__ fea
                 g[r][q][4] = __builtin_fma(rr[r][q], cc[r + 1][q], g[r][q][4]);
             }
     };
-    // UCH channels ((R + 1) x 16 bytes each) in flight per lane.  NT (non-temporal loads) measured 20 % SLOWER: every row is read
-    // a second time, right away, as the neighbour row of the wave above -- an L2 hit that `nt` gives up (profiles/archive/r04_gram_ab.txt)
-    auto ld2 = [](const double *q) -> d2_t {
-        if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(q));
-        else return *reinterpret_cast<const d2_t *>(q);
-    };
+    // UCH channels ((R + 1) x 16 bytes each) in flight per lane.  Non-temporal loads measured 20 % SLOWER: every row is read a
+    // second time, right away, as the neighbour row of the wave above -- an L2 hit they give up (profiles/archive/r04_gram_ab.txt)
+    auto ld2 = [](const double *q) -> d2_t { return *reinterpret_cast<const d2_t *>(q); };
     int c = 0;
     for (; c + UCH <= C; c += UCH) {
         d2_t v[UCH][R + 1];
@@ -2141,10 +2120,8 @@ static void launch_feat(const T *feat, long long bstride, int C, long long hw, i
 {
     dim3 grid(nblk, B), block(FTPB);
     constexpr int UNROLL = HALO_FEAT_UNROLL;      // channel planes in flight per lane (16: no gain beside the selection kernels, 6 % slower alone)
-    // granule of the XCD-contiguous chunk map: 256 chunks (512 KiB per plane), halved until a group of 8 granules fits
-    const char *eg = getenv("HALO_FEAT_XCD_GRANULE");      // A/B switch, read per call: -1 = the plain map
-    const int env_g = eg ? atoi(eg) : 256;
-    unsigned xcd_g = (unsigned)(env_g < 0 ? 0 : env_g);
+    // granule of the XCD-contiguous chunk map: 256 chunks (512 KiB per plane), halved until a group of 8 granules fits; 0 = the plain map
+    unsigned xcd_g = 256;
     while (xcd_g > 1 && 8 * xcd_g > (unsigned)nblk) xcd_g >>= 1;
     if (8 * xcd_g > (unsigned)nblk) xcd_g = 0;
 #define HALO_FEAT(M, FO_)                                                                                               \
@@ -2242,19 +2219,18 @@ static int launch_feat_lr(const T *feat, long long bstride, int C, const LrDims 
     nblk = (int)(grid.x * grid.y);
     if constexpr (sizeof(T) == 8) {
         // LDS-DMA double buffer (k_feat_reduce_lr_dma): float64, even source width (16-byte aligned pairs), at least 4 channels
-        // of the largest window per 16 KiB image; HALO_LR_NODMA=1 keeps the register-staged kernel (A/B switch, same bits)
+        // of the largest window per 16 KiB image; otherwise the register-staged kernel (same bits)
         const int units_per_ch = max_rows * ((max_cols + 2) / 2 + 1);        // even start column: up to one more pair per row
         int CCd = DMA_UNITS / units_per_ch;
         CCd = CCd > C ? C : CCd;
-        const bool dma_ok = lr.wf >= 2 && lr.wf % 2 == 0 && bstride % 2 == 0 && aligned16(feat) && CCd >= 4 && getenv("HALO_LR_NODMA") == nullptr;
+        const bool dma_ok = lr.wf >= 2 && lr.wf % 2 == 0 && bstride % 2 == 0 && aligned16(feat) && CCd >= 4;
         if (dma_ok) {
             const size_t lds = 2 * (size_t)DMA_UNITS * 16;
             // compile-time image geometries (k_feat_reduce_lr_dmaf): rows x pairs that cover the launch's largest window
             const int need_rows = max_rows, need_u = (max_cols + 2) / 2;
-            const bool nofixed = getenv("HALO_LR_NOFIXED") != nullptr;                 // A/B switch: runtime strides
             // 8 pixels per lane (64 x 32 output tiles) where a source row is at least 3 output rows tall: the row codes the kernel
-            // is instantiated for (HALO_LR_CODES8) then cover every wave; HALO_LR_PPT4=1 keeps the 4-pixel kernel (A/B, same bits)
-            if (!nofixed && (double)sh <= 1.0 / 3.0 && H >= 2 * LR_TH && getenv("HALO_LR_PPT4") == nullptr) {
+            // is instantiated for (HALO_LR_CODES8) then cover every wave; otherwise the 4-pixel kernel (same bits)
+            if ((double)sh <= 1.0 / 3.0 && H >= 2 * LR_TH) {
                 int max_rows8;
                 lr_window<T>(H, lr.hf, 2 * LR_TH, max_rows8);
                 ++max_rows8;
@@ -2271,7 +2247,7 @@ static int launch_feat_lr(const T *feat, long long bstride, int C, const LrDims 
 #undef HALO_LR_FIXED8
             }
 #define HALO_LR_FIXED(R_, U_)                                                                                                              \
-            if (!nofixed && need_rows <= R_ && need_u <= U_) {                                                                             \
+            if (need_rows <= R_ && need_u <= U_) {                                                                                         \
                 if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
                 else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
                 return HALO_OK;                                                                                                            \
@@ -2370,7 +2346,7 @@ static int score_impl(const float *logit, int64_t logit_bstride, const void *fea
         ? (((hw % 2 == 0) && (feat_bstride % 2 == 0) && aligned16(feat) && aligned16(imp_raw)) ? 2 : 1)
         : (((hw % 4 == 0) && (feat_bstride % 4 == 0) && aligned16(feat) && aligned16(imp_raw)) ? 4 : 1));
     const bool fuse = !lr && need_feat && ent_only && (O == 19 || O == 16) && fvec > 1 && (logit_bstride % fvec == 0) &&
-                      (((uintptr_t)logit) % (4 * fvec) == 0) && getenv("HALO_NO_FUSE") == nullptr;
+                      (((uintptr_t)logit) % (4 * fvec) == 0);
     FusedLogit fl{logit, (long long)logit_bstride, (int)O, unc_type, ent};
     const FusedLogit *flp = fuse ? &fl : nullptr;
     const bool need_logit_pass = !fuse && ( unc_type != HALO_UNC_ZEROS || pur_type == HALO_PUR_RIPU || pur_type == HALO_PUR_ORACLE_RIPU);
@@ -2411,28 +2387,23 @@ static int score_impl(const float *logit, int64_t logit_bstride, const void *fea
         if (ev_feat_start) (void)hipEventRecord((hipEvent_t)ev_feat_start, st);
         const int mode = pur_type == HALO_PUR_EUC_NORM ? 1 : 0;
         if (gram_mode) {
-            // 16 bytes per lane where the planes allow it (even width, 16-byte aligned); HALO_GRAM_8B=1: the 8-byte kernel (A/B)
-            const bool wide = lr->wf >= 2 && lr->wf % 2 == 0 && feat_bstride % 2 == 0 && aligned16(feat) && aligned16(gram) && getenv("HALO_GRAM_8B") == nullptr;
+            // 16 bytes per lane where the planes allow it (even width, 16-byte aligned); otherwise the 8-byte kernel
+            const bool wide = lr->wf >= 2 && lr->wf % 2 == 0 && feat_bstride % 2 == 0 && aligned16(feat) && aligned16(gram);
             if (wide) {
                 // rows per wave: every source row is loaded (R + 1) / R times (its own strip + as lower neighbour of the strip above),
                 // and that redundancy, not the bytes in flight, is what the kernel's time follows (profiles/archive/r04_gram_ab.txt: R = 2 / 4 /
                 // 8 -> 788 / 745 / 705 us per 16 images; 2, 3 or 4 channels in flight: equal; non-temporal loads: 20 % slower).  The
-                // widest strip that still gives every SIMD of the chip a wave; HALO_GRAM_ROWS / _UCH / _NT are A/B switches (same bits)
-                const char *eu = getenv("HALO_GRAM_UCH"), *en = getenv("HALO_GRAM_NT"), *er = getenv("HALO_GRAM_ROWS");
+                // widest strip that still gives every SIMD of the chip a wave; one channel in flight for 8-row strips, two otherwise
                 const long long nwx = cdiv(lr->wf, 128);
                 int rows = 2;
                 for (int cand = 8; cand > 2; cand >>= 1)
                     if (B * nwx * cdiv(lr->hf, cand) >= 1024) { rows = cand; break; }
-                if (er) rows = atoi(er);
-                rows = rows >= 8 ? 8 : (rows >= 4 ? 4 : 2);
-                const int uch = eu ? atoi(eu) : (rows == 8 ? 1 : 2), nt = en ? atoi(en) : 0;
                 const long long nwaves = nwx * cdiv(lr->hf, rows);
                 const dim3 gg((unsigned)(cdiv(cdiv(nwaves, TPB / 64), 8) * 8), (unsigned)B);
-#define HALO_GRAM2(U_, N_, R_) hipLaunchKernelGGL((k_gram_lr2<U_, N_, R_>), gg, block, 0, st, (const double *)feat, (long long)feat_bstride, (int)C, lr->hf, lr->wf, gram)
-                if (rows == 8) HALO_GRAM2(1, false, 8);
-                else if (rows == 4) { if (uch >= 3) HALO_GRAM2(3, false, 4); else if (uch == 2) HALO_GRAM2(2, false, 4); else HALO_GRAM2(1, false, 4); }
-                else if (uch >= 4) { if (nt) HALO_GRAM2(4, true, 2); else HALO_GRAM2(4, false, 2); }
-                else { if (nt) HALO_GRAM2(2, true, 2); else HALO_GRAM2(2, false, 2); }
+#define HALO_GRAM2(U_, R_) hipLaunchKernelGGL((k_gram_lr2<U_, R_>), gg, block, 0, st, (const double *)feat, (long long)feat_bstride, (int)C, lr->hf, lr->wf, gram)
+                if (rows == 8) HALO_GRAM2(1, 8);
+                else if (rows == 4) HALO_GRAM2(2, 4);
+                else HALO_GRAM2(2, 2);
 #undef HALO_GRAM2
             } else {
                 const long long nwaves = cdiv(lr->wf, GRAM_COLS) * cdiv(lr->hf, 2);
@@ -2492,15 +2463,14 @@ static int score_impl(const float *logit, int64_t logit_bstride, const void *fea
     const int do_box = (unc_type == HALO_UNC_ENTROPY || unc_type == HALO_UNC_ORACLE_ACC) ? 1 : 0;
     int nblk_unc = nblk1;
     const bool box3 = do_box && pad == HALO_PAD_ZEROS && ksize == 3 && W % 4 == 0 && aligned16(ent) && aligned16(unc_raw);   // (the 3x3 fast paths pad with zeros)
-    // 3 x 3 window + 16-byte aligned maps: the box sum is recomputed inside the combine kernel (no stored copy);
-    // HALO_NO_FUSE_TAIL=1 keeps the round-2 sequence (A/B switch, identical results)
+    // 3 x 3 window + 16-byte aligned maps: the box sum is recomputed inside the combine kernel (no stored copy); otherwise the
+    // round-2 sequence (k_box3_unc / k_box_unc + k_combine, identical results)
     const bool fuse_tail = box3 && B <= 65535 && H <= 65535 && aligned16(imp_raw) && aligned16(score) && (!impurity || aligned16(impurity)) &&
-                           (!uncertainty || aligned16(uncertainty)) && (!active || ((uintptr_t)active & 3) == 0) &&
-                           getenv("HALO_NO_FUSE_TAIL") == nullptr;
+                           (!uncertainty || aligned16(uncertainty)) && (!active || ((uintptr_t)active & 3) == 0);
     const int nblk_c3 = (int)cdiv(hw, TPB * 4);
     // the selector's coarse histogram of a normalised score map, counted by the combine kernel while it writes the map and handed
-    // over behind the range records (HALO_NO_FUSE_HIST=1: A/B switch, the selector then counts it itself -- same picks)
-    unsigned *rng_hist = (score_range && normalize && fuse_tail && getenv("HALO_NO_FUSE_HIST") == nullptr)
+    // over behind the range records (otherwise the selector counts it itself -- same picks)
+    unsigned *rng_hist = (score_range && normalize && fuse_tail)
                              ? (unsigned *)((char *)score_range + range_hist_offset(B)) : nullptr;
     if (fuse_tail) {
         if (normalize) {            // only the min / max are needed before the combine kernel
@@ -2528,11 +2498,9 @@ static int score_impl(const float *logit, int64_t logit_bstride, const void *fea
         int crows = CB_ROWS;                 // rows per workgroup: as many as leave >= 1024 workgroups in the launch
         while (crows > 1 && cdiv(W, TPB * 4) * cdiv(H, crows) * B < 1024) crows >>= 1;
         dim3 gridc((unsigned)cdiv(W, TPB * 4), (unsigned)cdiv(H, crows), (unsigned)B);
-        // non-temporal impurity / uncertainty stores measured SLOWER (233 against 214 us per 16 images, gpurun_out/r05f): off unless asked for
-        static const bool cb_nt = getenv("HALO_COMBINE_NT") != nullptr;      // A/B switch (same bits)
-#define HALO_CB(T, NT_) hipLaunchKernelGGL((k_combine_box3<T, NT_>), gridc, block, 0, st, (const T *)imp_raw, (const float *)ent, stats, active, (int)H, (int)W, hist ? pksize : 0, normalize, (T *)score, (T *)impurity, uncertainty, rng_free, rng_hist, crows)
-        if (f64out) { if (cb_nt) HALO_CB(double, true); else HALO_CB(double, false); }
-        else { if (cb_nt) HALO_CB(float, true); else HALO_CB(float, false); }
+#define HALO_CB(T) hipLaunchKernelGGL((k_combine_box3<T>), gridc, block, 0, st, (const T *)imp_raw, (const float *)ent, stats, active, (int)H, (int)W, hist ? pksize : 0, normalize, (T *)score, (T *)impurity, uncertainty, rng_free, rng_hist, crows)
+        if (f64out) HALO_CB(double);
+        else HALO_CB(float);
 #undef HALO_CB
     } else if (f64out) hipLaunchKernelGGL((k_combine<double>), grid1, block, 0, st, (const double *)imp_raw, unc_raw, stats, active, hw, normalize, (double *)score, (double *)impurity, uncertainty);
     else hipLaunchKernelGGL((k_combine<float>), grid1, block, 0, st, (const float *)imp_raw, unc_raw, stats, active, hw, normalize, (float *)score, (float *)impurity, uncertainty);

@@ -845,13 +845,6 @@ using namespace halo;
 
 namespace halo {
 
-static unsigned sel_target()
-{
-    const char *e = getenv("HALO_SEL_TARGET");       // tuning aid: expected candidates per fine bin
-    const int v = e ? atoi(e) : 0;
-    return v >= 8 && v <= BIN_CAP / 2 ? (unsigned)v : (unsigned)(BIN_CAP / 2);      // bins are Poisson-filled: keep 2x headroom
-}
-
 BinPlan binned_plan(int64_t B, int64_t H, int64_t W, int64_t n_regions, int64_t arad, int64_t mrad)
 {
     BinPlan p;
@@ -874,7 +867,7 @@ BinPlan binned_plan(int64_t B, int64_t H, int64_t W, int64_t n_regions, int64_t 
     if (cap > hw) cap = hw;
     g.kneed = (unsigned)kneed;
     g.captot = (unsigned)cap;
-    g.target = sel_target();
+    g.target = (unsigned)(BIN_CAP / 2);       // expected candidates per fine bin: bins are Poisson-filled, keep 2x headroom
     g.nfmax = (unsigned)(cap / g.target + NB1 + 1);
     size_t o = 0;
     auto take = [&](size_t per_image) { const size_t at = o; o += align_up(per_image * (size_t)B, 256); return at; };

@@ -118,7 +118,7 @@ for i in range(N):
     if i % 25 == 0:
         print("case %d ok %s" % (i, dict(desc, O=O, H2=H2, W2=W2)), flush=True)
 # the fused native HyperMLR backward (halo_hypermlr_backward: <= 20 classes, 64 | C <= 256) against the term-map path it replaces
-from halo_amd.core.utils.hyperbolic import _HyperMLRFn
+from halo_amd.core.utils.hyperbolic import _HyperMLRFn, mlr_backward_terms
 for i in range(max(1, N // 10)):
     c = float(rng.choice([1.0, 1.0, 0.5, 2.0, 0.1]))
     B, C, O = int(rng.integers(1, 4)), int(rng.choice([64, 64, 128, 192, 256])), int(rng.integers(1, 21))
@@ -131,16 +131,9 @@ for i in range(max(1, N // 10)):
     x0 = HyperMapper(c).expmap(t(z), dim=1).double()
     bound = 1.0 / np.sqrt(C)
     P0, A0, Wt = t(rng.uniform(-bound, bound, (O, C))), t(rng.uniform(-bound, bound, (O, C))), t(rng.standard_normal((B, O, h, w)))
-    res = []
-    for env in (None, "1"):
-        if env:
-            os.environ["HALO_MLR_BWD_TERMS"] = env
-        else:
-            os.environ.pop("HALO_MLR_BWD_TERMS", None)
-        xg, Pg, Ag = x0.clone().requires_grad_(True), P0.clone().requires_grad_(True), A0.clone().requires_grad_(True)
-        (_HyperMLRFn.apply(xg, Pg, Ag, c) * Wt).sum().backward()
-        res.append([g.grad.cpu().numpy() for g in (xg, Pg, Ag)])
-    os.environ.pop("HALO_MLR_BWD_TERMS", None)
+    xg, Pg, Ag = x0.clone().requires_grad_(True), P0.clone().requires_grad_(True), A0.clone().requires_grad_(True)
+    (_HyperMLRFn.apply(xg, Pg, Ag, c) * Wt).sum().backward()
+    res = [[g.grad.cpu().numpy() for g in (xg, Pg, Ag)], [g.cpu().numpy() for g in mlr_backward_terms(x0, P0, A0, Wt, c)]]
     for name, a_, b_ in zip(("gx", "gP", "gA"), res[0], res[1]):
         r = float(np.abs(a_ - b_).max() / (np.abs(b_).max() + 1e-300))
         worst["mlr backward " + name] = max(worst.get("mlr backward " + name, 0.0), r)

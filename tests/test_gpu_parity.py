@@ -36,24 +36,13 @@ def t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-class _env_set:
-    """context manager: os.environ entries set for the block, restored after"""
-    def __init__(self, env):
-        self.env, self.old = env, {}
-
-    def __enter__(self):
-        import os
-        for k, v in self.env.items():
-            self.old[k] = os.environ.get(k)
-            os.environ[k] = v
-
-    def __exit__(self, *exc):
-        import os
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+def _offset_copy(x, off=1):
+    """x's values `off` elements past the start of a larger allocation (a contiguous view with a storage offset): the same input
+    at an address that is no longer 16-byte aligned, which routes the dispatchers to their unaligned kernels and vector widths"""
+    buf = torch.empty(x.numel() + off, dtype=x.dtype, device=x.device)
+    v = buf[off:].view(x.shape)
+    v.copy_(x)
+    return v
 
 
 def _with_env(env, fn):
@@ -313,7 +302,8 @@ def test_odd_sizes_take_the_scalar_paths(dev):
 def test_histogram_class_sum_follows_torchs_cascade_for_any_bin_count(dev, K):
     """compute_region_impurity sums K one-hot channels with torch.sum, whose accumulator cascade flushes every 16 / 256 / 4096 terms
     (oracle: ATen's loop literally; device: the flush decided from the class index alone, ClassSum in halo_score.hip): both window
-    kernels against the oracle bit for bit with bins on either side of every flush boundary."""
+    kernels against the oracle bit for bit with bins on either side of every flush boundary (the generic kernel at 3 x 3 through
+    'reflect' padding, which the LDS-tile kernel does not serve)."""
     from halo_amd.core.active.floating_region import score_maps
     from oracle import halo_oracle as ho
     rng = np.random.default_rng(K)
@@ -321,11 +311,11 @@ def test_histogram_class_sum_follows_torchs_cascade_for_any_bin_count(dev, K):
     logit = rng.standard_normal((1, O, H, W)).astype(np.float32)
     emb = rng.standard_normal((1, C, H, W)) * rng.uniform(0.01, 0.6, (1, 1, H, W))          # radii spread over the whole bin range
     gt = rng.integers(0, O, (H, W)).astype(np.int64)
-    for size, env in ((3, {}), (3, {"HALO_IMPURITY_GENERIC": "1"}), (5, {})):
-        so, io, uo = ho.floating_region_score(logit, emb, "entropy", "hyper", True, gt, size=size, purity_type="hyper", K=K)
+    for size, pad in ((3, "zeros"), (3, "reflect"), (5, "zeros")):
+        so, io, uo = ho.floating_region_score(logit, emb, "entropy", "hyper", True, gt, size=size, purity_type="hyper", K=K, padding_mode=pad)
         # (the module forces the 'hyper' purity window to 3 x 3 whatever `size` is, floating_region.py:54-55; score_maps takes it explicitly)
-        s, i, u = _with_env(env, lambda: score_maps(t(logit, dev), t(emb, dev), "entropy", "hyper", True, t(gt, dev)[None], size=size, purity_size=3, K=K))
-        assert bits_equal(i[0].cpu().numpy(), io) and bits_equal(u[0].cpu().numpy(), uo) and bits_equal(s[0].cpu().numpy(), so), (K, size, env)
+        s, i, u = score_maps(t(logit, dev), t(emb, dev), "entropy", "hyper", True, t(gt, dev)[None], size=size, purity_size=3, K=K, padding_mode=pad)
+        assert bits_equal(i[0].cpu().numpy(), io) and bits_equal(u[0].cpu().numpy(), uo) and bits_equal(s[0].cpu().numpy(), so), (K, size, pad)
 
 
 def test_wider_windows(dev):
@@ -976,10 +966,11 @@ def test_selection_with_the_scorers_range_records(dev):
     assert bits_equal(outs[0], outs[1])
 
 
-def test_fused_selector_histogram_is_consumed_once_and_survives_a_changed_map(dev, monkeypatch):
+def test_fused_selector_histogram_is_consumed_once_and_survives_a_changed_map(dev):
     """Round 4: for normalised maps the combine kernel counts the selector's 2048-bin coarse histogram while it
     writes the score and hands it over behind the range records; the selector skips its own pass over the map.  (1) same picks,
-    tables and masks as with HALO_NO_FUSE_HIST=1 (the selector counts) and as without any record; (2) the counts describe the
+    tables and masks as when the selector counts it itself (the same prior-pick mask at an unaligned address: the combine kernel
+    that counts does not serve it) and as without any record; (2) the counts describe the
     map as it was scored: a SECOND selection with the same records (windows now -inf) must not trust them -- the flag is consumed
     by the first; (3) a map the caller changed between scoring and selection (a large region masked by hand, so that fewer
     candidates exist above the threshold than the counts promise) still selects exactly what the unranged path selects: the sweep
@@ -995,10 +986,11 @@ def test_fused_selector_histogram_is_consumed_once_and_survives_a_changed_map(de
     act0 = rng.random((B, H, W)) < 0.02
     lg, em = t(logit, dev), t(emb, dev)
 
-    def run(ranged, n, premask=None, twice=False):
+    def run(ranged, n, premask=None, twice=False, unaligned=False):
         rec = new_score_range(B, dev) if ranged else None
         act = t(act0, dev).clone()
-        sc = score_maps(lg, em, "entropy", "radius", True, None, size=3, active=act, want_maps=False, score_range=rec)[0]
+        sc = score_maps(lg, em, "entropy", "radius", True, None, size=3, active=_offset_copy(act) if unaligned else act, want_maps=False,
+                        score_range=rec)[0]
         if premask is not None:
             sc[premask] = -float("inf")
         sel = torch.zeros_like(act)
@@ -1012,9 +1004,7 @@ def test_fused_selector_histogram_is_consumed_once_and_survives_a_changed_map(de
     n = 40
     base = run(False, n)
     fused = run(True, n)
-    monkeypatch.setenv("HALO_NO_FUSE_HIST", "1")
-    unfused = run(True, n)
-    monkeypatch.delenv("HALO_NO_FUSE_HIST")
+    unfused = run(True, n, unaligned=True)
     for other in (fused, unfused):
         assert bits_equal(base[0][0][0], other[0][0][0]) and np.array_equal(base[0][0][1], other[0][0][1])
         assert all(np.array_equal(x, y) for x, y in zip(base[1:4], other[1:4])) and bits_equal(base[4], other[4])
@@ -1210,22 +1200,40 @@ def test_padding_modes_vs_reference_and_oracle(golden, dev, mode):
         score_maps(tiny, None, "entropy", "ripu", False, None, size=3, padding_mode="mirror")
 
 
-@pytest.mark.parametrize("rows", ["2", "4", "8"])
-def test_gram_kernel_strip_heights_are_invisible(dev, monkeypatch, rows):
-    """k_gram_lr2 lets a wave own 2, 4 or 8 source rows (chosen by the size of the launch; HALO_GRAM_ROWS forces one): same fma
-    chains per low-res pixel whatever the strip, so the maps are bit-identical to the oracle twin for every strip height --
-    source heights that are no multiple of the strip, shorter than it, a single row, odd widths (the 8-byte kernel) included."""
+def _gram_strip_batch(hf, wf, rows):
+    """the batch at which the launch of k_gram_lr2 picks `rows` source rows per wave (the host's rule in halo_score.hip: the widest
+    strip that leaves >= 1024 waves), or None when no batch does (a strip of 4 where 4 and 8 rows give the same wave count)"""
+    nwx, cdiv = -(-wf // 128), lambda a, b: -(-a // b)
+    if rows == 2:
+        return 2 if 2 * nwx * cdiv(hf, 4) < 1024 else None
+    B = 2 * cdiv(cdiv(1024, nwx * cdiv(hf, rows)), 2)                 # (even: copies of two images)
+    return B if rows == 8 or B * nwx * cdiv(hf, 8) < 1024 else None
+
+
+@pytest.mark.parametrize("rows", [2, 4, 8])
+def test_gram_kernel_strip_heights_are_invisible(dev, rows):
+    """k_gram_lr2 lets a wave own 2, 4 or 8 source rows, chosen by the size of the launch: same fma chains per low-res pixel
+    whatever the strip, so the maps are bit-identical to the oracle twin for every strip height -- source heights that are no
+    multiple of the strip, shorter than it, a single row, odd widths (the 8-byte kernel) included.  Each strip is reached by a
+    batch of copies of two images large enough for the launch to pick it; every copy must give its image's bits."""
     from halo_amd.core.active.floating_region import score_maps_lowres
     from oracle import halo_oracle as ho
-    monkeypatch.setenv("HALO_GRAM_ROWS", rows)
-    rng = np.random.default_rng(int(rows))
+    rng = np.random.default_rng(rows)
     for (C, hf, wf, H, W) in ((24, 16, 32, 64, 128), (7, 9, 130, 30, 300), (5, 1, 64, 4, 200), (12, 3, 6, 17, 23), (9, 21, 258, 40, 500),
                               (6, 7, 5, 20, 16), (256, 32, 64, 64, 128)):
+        B = _gram_strip_batch(hf, wf, rows) if wf % 2 == 0 else (2 if rows == 2 else None)     # (odd widths: the 8-byte kernel, no strips)
+        if B is None:
+            continue
         emb_lr = ho.expmap((rng.standard_normal((2, C, hf, wf)) * 0.3).astype(np.float32), 1.0, dim=1)
         logit_lr = rng.standard_normal((2, 19, 8, 8)).astype(np.float32)
-        g = score_maps_lowres(t(logit_lr, dev), t(emb_lr, dev), (H, W), "none", "radius", False, None, ksize=3, mode="gram")[1].cpu().numpy()
+        reps = B // 2
+        em = t(emb_lr, dev).repeat(reps, 1, 1, 1)
+        g = score_maps_lowres(t(logit_lr, dev).repeat(reps, 1, 1, 1), em, (H, W), "none", "radius", False, None, ksize=3, mode="gram")[1].cpu().numpy()
+        del em
         for b in range(2):
-            assert bits_equal(g[b], ho.gram_radius(emb_lr[b], (H, W), "radius", 1.0)), (rows, C, hf, wf, b)
+            want = ho.gram_radius(emb_lr[b], (H, W), "radius", 1.0)
+            for k in range(b, B, 2):
+                assert bits_equal(g[k], want), (rows, C, hf, wf, B, k)
 
 
 def test_lowres_gram_mode_on_degenerate_grids(dev):
@@ -1295,9 +1303,10 @@ def test_lowres_downsampling_falls_back_to_explicit_upsample(dev):
 
 
 def test_hypermlr_matrix_core_path_matches_valu_path(golden, dev):
-    """halo_hypermlr_logits runs its contractions on v_mfma_f64_16x16x4_f64 (<= 32 classes); the VALU
-    kernel (one fma chain per pixel/class, HALO_MLR_VALU=1) is the in-library cross-check."""
-    import os
+    """halo_hypermlr_logits runs its contractions on v_mfma_f64_16x16x4_f64 (<= 32 classes); the VALU kernel (one fma chain per
+    pixel/class, more than 32 classes) is the in-library cross-check: class logits are independent, so a 33-class layer whose first
+    O rows are the test's P / A gives the VALU kernel's statement of the same O columns.  The same x at an 8-byte-aligned address
+    takes the chunked matrix-core kernel (the round-1 kernel) instead of the weights-resident one."""
     from halo_amd.core.utils.hyperbolic import HyperMLR
     from oracle import halo_oracle as ho
     rng = np.random.default_rng(21)
@@ -1307,16 +1316,14 @@ def test_hypermlr_matrix_core_path_matches_valu_path(golden, dev):
         x[0, :, 0, 0] = 0.0
         mlr = HyperMLR(C, O, c=1.0).to(dev)
         want = ho.hypermlr(x, mlr.P_MLR.detach().cpu().numpy(), mlr.A_MLR.detach().cpu().numpy(), 1.0)
+        wide = HyperMLR(C, 33, c=1.0).to(dev)                   # classes O..32 only pad the layer past the matrix-core kernels' 32
         with torch.no_grad():
-            os.environ.pop("HALO_MLR_VALU", None)
+            wide.P_MLR[:O].copy_(mlr.P_MLR)
+            wide.A_MLR[:O].copy_(mlr.A_MLR)
             a = mlr(t(x, dev)).cpu().numpy()
             a32 = mlr._hyper_logits(t(x, dev), out_dtype=torch.float32).cpu().numpy()
-            os.environ["HALO_MLR_VALU"] = "1"
-            try:
-                v = mlr(t(x, dev)).cpu().numpy()
-            finally:
-                os.environ.pop("HALO_MLR_VALU", None)
-            ch = _with_env({"HALO_MLR_CHUNKED": "1"}, lambda: mlr(t(x, dev)).cpu().numpy())       # round-1 matrix-core kernel
+            v = wide(t(x, dev))[:, :O].cpu().numpy()
+            ch = mlr(_offset_copy(t(x, dev))).cpu().numpy()
         assert max_abs_diff(a, want) < 1e-11 and max_abs_diff(v, want) < 1e-11 and max_abs_diff(ch, want) < 1e-11
         assert max_abs_diff(a, v) < 1e-12 and max_abs_diff(a, ch) < 1e-12
         assert np.abs(a32 - want.astype(np.float32)).max() < 1e-5
@@ -1336,7 +1343,7 @@ def test_fused_head_tail_equals_the_two_kernel_path_bit_for_bit(dev, B, O, h, w,
     552-558) against the two calls it replaces: the SAME embedding and the SAME logits, bit for bit -- ordinary pixels, pixels far
     outside the ball (tanh clamp + projection), an exact-origin pixel, pixel counts that leave the last 32-pixel tile ragged,
     2 / 16 / 19 / 24 / 32 classes (all three column-tile counts), float32 and float64 logits, curvatures != 1; and the embedding
-    within the oracle's tolerance.  HALO_HEAD_TAIL_SPLIT=1 and shapes the kernel does not serve take the two-kernel path."""
+    within the oracle's tolerance.  Shapes the kernel does not serve take the two-kernel path."""
     from halo_amd.core.models.classifier import hyper_head_tail
     from halo_amd.core.utils.hyperbolic import HyperMapper, HyperMLR, head_tail_fused
     from oracle import halo_oracle as ho
@@ -1366,10 +1373,11 @@ def test_fused_head_tail_equals_the_two_kernel_path_bit_for_bit(dev, B, O, h, w,
     assert bits_equal(emb_f.cpu().numpy(), emb_s.cpu().numpy()), "embedding differs from k_expmap0_project's"
     assert bits_equal(out_f.cpu().numpy(), out_s.cpu().numpy()), "logits differ from k_hypermlr_mfma_res's"
     assert np.abs(emb_f.cpu().numpy() - ho.expmap(z, c, dim=1)).max() < 1e-14
-    # the head-tail function itself: fused by default, the two kernels under the switch, other channel counts as before
+    # the head-tail function itself: fused, against the explicit two calls (expmap + HyperMLR -> float32); other channel counts as before
     with torch.no_grad():
         o1, e1 = hyper_head_tail(zt, mapper, mlr)
-        o2, e2 = _with_env({"HALO_HEAD_TAIL_SPLIT": "1"}, lambda: hyper_head_tail(zt, mapper, mlr))
+        e2 = mapper.expmap(zt, dim=1)
+        o2 = mlr._hyper_logits(e2, out_dtype=torch.float32)
         o3, e3 = hyper_head_tail(zt[:, :48].contiguous(), mapper, HyperMLR(48, O, c=c).to(dev))
     assert bits_equal(o1.cpu().numpy(), o2.cpu().numpy()) and bits_equal(e1.cpu().numpy(), e2.cpu().numpy())
     assert e3.shape[1] == 48 and bool(torch.isfinite(o3).all())
@@ -1589,44 +1597,51 @@ def test_head_tail_gradients_match_reference_autograd(golden, dev):
     """d loss / d {feat, P_MLR, A_MLR, embed} of the head tail (classifier.py:553-554) from the HIP backward
     kernels + library GEMMs vs the reference's own autograd (tests/golden/grads.npz), including
     tanh-clamped / projected pixels and an exact-origin pixel."""
-    from halo_amd.core.utils.hyperbolic import HyperMapper, HyperMLR
+    from halo_amd.core.utils.hyperbolic import HyperMapper, HyperMLR, mlr_backward_terms
     d = golden("grads")
     # c64_o19 is the head's own 64 x 19: the fused native backward (halo_hypermlr_backward); the same vectors once more through the
-    # term-map path (HALO_MLR_BWD_TERMS=1), which is what the two smaller cases take anyway
-    for tag, env in (("c8_o19", {}), ("c16_o16_k07", {}), ("c64_o19", {}), ("c64_o19", {"HALO_MLR_BWD_TERMS": "1"})):
-      with _env_set(env):
-          c = float(d[tag + "__c"][0])
-          z = t(d[tag + "__z"], dev).requires_grad_(True)
-          O, C = d[tag + "__P"].shape
-          mlr = HyperMLR(C, O, c=c).to(dev)
-          with torch.no_grad():
-              mlr.P_MLR.copy_(t(d[tag + "__P"], dev)); mlr.A_MLR.copy_(t(d[tag + "__A"], dev))
-          embed = HyperMapper(c=c).expmap(z, dim=1)
-          embed.retain_grad()
-          logits = mlr(embed.double()).float()
-          assert max_abs_diff(embed.detach().cpu().numpy(), d[tag + "__embed"]) < 1e-14
-          assert np.abs(logits.detach().cpu().numpy() - d[tag + "__logits"]).max() < 1e-5
-          loss = (logits * t(d[tag + "__Wt"], dev)).sum() + (embed * t(d[tag + "__Ve"], dev)).sum()
-          loss.backward()
+    # term-map path (mlr_backward_terms), which is what the two smaller cases take anyway
+    for tag, terms in (("c8_o19", False), ("c16_o16_k07", False), ("c64_o19", False), ("c64_o19", True)):
+        c = float(d[tag + "__c"][0])
+        z = t(d[tag + "__z"], dev).requires_grad_(True)
+        O, C = d[tag + "__P"].shape
+        mlr = HyperMLR(C, O, c=c).to(dev)
+        with torch.no_grad():
+            mlr.P_MLR.copy_(t(d[tag + "__P"], dev)); mlr.A_MLR.copy_(t(d[tag + "__A"], dev))
+        embed = HyperMapper(c=c).expmap(z, dim=1)
+        embed.retain_grad()
+        logits = mlr(embed.double()).float()
+        assert max_abs_diff(embed.detach().cpu().numpy(), d[tag + "__embed"]) < 1e-14
+        assert np.abs(logits.detach().cpu().numpy() - d[tag + "__logits"]).max() < 1e-5
+        loss = (logits * t(d[tag + "__Wt"], dev)).sum() + (embed * t(d[tag + "__Ve"], dev)).sum()
+        if terms:
+            # d loss / d logits = Wt (float32, as autograd hands it to the HyperMLR backward), d loss / d embed = the backward's d x + Ve
+            gx, gP, gA = mlr_backward_terms(embed.detach(), mlr.P_MLR.detach(), mlr.A_MLR.detach(), t(d[tag + "__Wt"], dev).float(), c)
+            embed.backward(gx + t(d[tag + "__Ve"], dev))
+            mlr.P_MLR.grad, mlr.A_MLR.grad = gP, gA
+        else:
+            loss.backward()
 
-          def rel(a, b):
-              return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
-          assert z.grad.dtype == torch.float32 and mlr.P_MLR.grad.dtype == torch.float64
-          assert rel(embed.grad.cpu().numpy(), d[tag + "__g_embed"]) < 1e-10, tag
-          assert rel(mlr.P_MLR.grad.cpu().numpy(), d[tag + "__g_P"]) < 1e-10, tag
-          assert rel(mlr.A_MLR.grad.cpu().numpy(), d[tag + "__g_A"]) < 1e-10, tag
-          assert rel(z.grad.cpu().numpy(), d[tag + "__g_z"]) < 2e-6, tag                     # float32 gradient
-          # per-pixel check incl. the clamped / projected / origin pixels
-          gz, want = z.grad.cpu().numpy(), d[tag + "__g_z"]
-          assert np.abs(gz - want).max() <= 2e-6 * np.abs(want).max() + 1e-7
+        def rel(a, b):
+            return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
+        assert z.grad.dtype == torch.float32 and mlr.P_MLR.grad.dtype == torch.float64
+        assert rel(embed.grad.cpu().numpy(), d[tag + "__g_embed"]) < 1e-10, tag
+        assert rel(mlr.P_MLR.grad.cpu().numpy(), d[tag + "__g_P"]) < 1e-10, tag
+        assert rel(mlr.A_MLR.grad.cpu().numpy(), d[tag + "__g_A"]) < 1e-10, tag
+        assert rel(z.grad.cpu().numpy(), d[tag + "__g_z"]) < 2e-6, tag                     # float32 gradient
+        # per-pixel check incl. the clamped / projected / origin pixels
+        gz, want = z.grad.cpu().numpy(), d[tag + "__g_z"]
+        assert np.abs(gz - want).max() <= 2e-6 * np.abs(want).max() + 1e-7
 
 
 def test_hypermlr_fused_backward_matches_term_path(dev):
     """halo_hypermlr_backward (three kernels: reverse sweep + d x, d W partials, parameter algebra) against the term-map path
-    (reverse-sweep kernel + library GEMMs, HALO_MLR_BWD_TERMS=1) it replaces at the heads' shapes: the same per-element sweep,
+    (reverse-sweep kernel + library GEMMs, mlr_backward_terms) it replaces at the heads' shapes: the same per-element sweep,
     sums in another order.  Shapes: ragged pixel counts (a partial last workgroup, an odd chunk), 1-4 channel blocks, 1-20
-    classes, pixels beyond the projection limit, an exact-origin pixel; and twice the same call -> the same bits."""
-    from halo_amd.core.utils.hyperbolic import HyperMapper, _HyperMLRFn
+    classes, pixels beyond the projection limit, an exact-origin pixel; and twice the same call -> the same bits.  The pixel
+    kernel's two weight arms (an LDS image below B * hw = 400 000 pixels, the scalar cache above) run the same fma chains: copies
+    of the batch past the threshold must give every copy the d x bits of the small batch."""
+    from halo_amd.core.utils.hyperbolic import HyperMapper, _HyperMLRFn, mlr_backward_terms
     rng = np.random.default_rng(91)
     for (B, C, O, h, w, c) in ((2, 64, 19, 24, 40, 1.0), (1, 128, 19, 9, 7, 1.0), (1, 256, 5, 5, 13, 0.7), (2, 192, 20, 8, 8, 1.0),
                                (3, 64, 1, 1, 3, 1.0), (1, 64, 19, 33, 129, 1.3)):
@@ -1637,26 +1652,33 @@ def test_hypermlr_fused_backward_matches_term_path(dev):
         bound = 1.0 / np.sqrt(C)
         P0, A0 = t(rng.uniform(-bound, bound, (O, C)), dev), t(rng.uniform(-bound, bound, (O, C)), dev)
         Wt = t(rng.standard_normal((B, O, h, w)), dev)
-        res = []
-        # 0, 1: the default twice   2: the pixel kernel's weights from LDS   3: its weights through the scalar cache   4: the term-map path
-        # 5: the two separate d x / d W kernels instead of the one-pass kernel
-        for env in ({}, {}, {"HALO_MLR_BWD_W": "lds"}, {"HALO_MLR_BWD_W": "scalar"}, {"HALO_MLR_BWD_TERMS": "1"}, {"HALO_MLR_BWD_DXW": "0"}):
-            with _env_set(env):
-                x, P, A = x0.clone().requires_grad_(True), P0.clone().requires_grad_(True), A0.clone().requires_grad_(True)
-                (_HyperMLRFn.apply(x, P, A, c) * Wt).sum().backward()
-                res.append([g.grad.cpu().numpy() for g in (x, P, A)])
+        assert B * h * w < 400000                               # these shapes: the pixel kernel's weights from LDS
+
+        def fused(xv, Wv):
+            x, P, A = xv.clone().requires_grad_(True), P0.clone().requires_grad_(True), A0.clone().requires_grad_(True)
+            (_HyperMLRFn.apply(x, P, A, c) * Wv).sum().backward()
+            return [g.grad.cpu().numpy() for g in (x, P, A)]
+
+        def terms(xv, Wv):
+            return [g.cpu().numpy() for g in mlr_backward_terms(xv, P0, A0, Wv, c)]
+        res = [fused(x0, Wt), fused(x0, Wt), terms(x0, Wt)]             # the default twice, the term-map path
         for a_, b_ in zip(res[0], res[1]):
             assert np.array_equal(a_, b_), "the fused backward is not deterministic"
-        for a_, b_ in zip(res[2], res[3]):
-            assert np.array_equal(a_, b_), "the two weight paths of the pixel kernel run the same fma chains: same bits"
-        # the two separate d x / d W kernels against the one-pass kernel: the same MFMA chains for d x (same bits), other partial sums for d W
-        assert np.array_equal(res[5][0], res[2][0]), "d x of the one-pass kernel differs from the d x kernel's"
-        for name, a_, b_ in zip(("gP", "gA"), res[5][1:], res[2][1:]):
-            assert np.abs(a_ - b_).max() <= 1e-12 * np.abs(b_).max() + 1e-300, ("two kernels", name, B, C, O, h, w)
-        for other, tag in ((2, "weights from LDS"), (4, "term maps")):
-            for name, a_, b_ in zip(("gx", "gP", "gA"), res[0], res[other]):
-                assert np.isfinite(a_).all(), (name, B, C, O)
-                assert np.abs(a_ - b_).max() <= 1e-11 * np.abs(b_).max() + 1e-300, (tag, name, B, C, O, h, w, float(np.abs(a_ - b_).max()), float(np.abs(b_).max()))
+        for name, a_, b_ in zip(("gx", "gP", "gA"), res[0], res[2]):
+            assert np.isfinite(a_).all(), (name, B, C, O)
+            assert np.abs(a_ - b_).max() <= 1e-11 * np.abs(b_).max() + 1e-300, ("term maps", name, B, C, O, h, w, float(np.abs(a_ - b_).max()), float(np.abs(b_).max()))
+        # k copies of the batch: >= 400 000 pixels, the weights through the scalar cache.  d x is per pixel (same bits in every copy);
+        # d P and d A are sums over all pixels and keep their bar against the term-map path of the same batch.  (At 3 pixels per
+        # image no call of at most 65535 images reaches the scalar arm.)
+        k = -(-400000 // (B * h * w))
+        if k * B <= 65535:
+            xk, Wk = x0.repeat(k, 1, 1, 1), Wt.repeat(k, 1, 1, 1)
+            big, big_t = fused(xk, Wk), terms(xk, Wk)
+            for j in range(k):
+                assert np.array_equal(big[0][j * B:(j + 1) * B], res[0][0]), "the two weight paths of the pixel kernel run the same fma chains: same bits"
+            for name, a_, b_ in zip(("gP", "gA"), big[1:], big_t[1:]):
+                assert np.abs(a_ - b_).max() <= 1e-11 * np.abs(b_).max() + 1e-300, ("scalar weights", name, B, C, O, h, w)
+            del xk, Wk, big, big_t
         # float32 logits straight from the forward kernel and a float32 gradient straight into the backward (the head's `.float()`
         # fused at both ends): the bits of the float64 route with the cast outside
         W32 = Wt.float()
@@ -1776,26 +1798,22 @@ def test_bench_data_variants_on_a_small_shape(dev, data):
 
 
 def test_fused_and_unfused_entropy_paths_agree_bitwise(dev):
-    """k_feat_reduce with the fused per-pixel entropy vs the stand-alone k_logit_maps kernel (HALO_NO_FUSE=1)."""
+    """k_feat_reduce with the fused per-pixel entropy vs the stand-alone k_logit_maps kernel: the same embedding at an address that
+    is not 16-byte aligned takes the one-pixel-per-lane feature kernel, which does not fuse the logits."""
     from halo_amd.core.active.floating_region import score_maps
     for dt in (np.float64, np.float32):
         logit, emb, gt = _synthetic(128, 256, 24, 19, 5, dt)
-        args = (t(logit, dev), t(emb, dev), "entropy", "radius", True, None)
-        os.environ.pop("HALO_NO_FUSE", None)
-        a = score_maps(*args, size=3)
-        os.environ["HALO_NO_FUSE"] = "1"
-        try:
-            b = score_maps(*args, size=3)
-        finally:
-            os.environ.pop("HALO_NO_FUSE", None)
+        lg, em = t(logit, dev), t(emb, dev)
+        a = score_maps(lg, em, "entropy", "radius", True, None, size=3)
+        b = score_maps(lg, _offset_copy(em), "entropy", "radius", True, None, size=3)
         for x, y in zip(a, b):
             assert bits_equal(x.cpu().numpy(), y.cpu().numpy())
 
 
 def test_fused_tail_equals_the_round2_tail_bitwise(dev):
     """Round 3: the 3x3 box sum recomputed inside the combine kernel (k_combine_box3, edge taps through lane shifts) and
-    the single finalize launch vs the round-2 sequence k_box3_unc -> 2 x finalize -> k_combine (HALO_NO_FUSE_TAIL=1), and
-    both against the oracle: every branch that box-sums, normalised or not, with and without the prior-pick mask,
+    the single finalize launch vs the round-2 sequence k_box3_unc -> 2 x finalize -> k_combine (which serves a score map at an
+    address that is not 16-byte aligned), and both against the oracle: every branch that box-sums, normalised or not, with and without the prior-pick mask,
     widths that are and are not multiples of a wave's 256 pixels (rows that start inside a wave), single-row images."""
     from halo_amd.core.active.floating_region import score_maps
     from oracle import halo_oracle as ho
@@ -1813,7 +1831,7 @@ def test_fused_tail_equals_the_round2_tail_bitwise(dev):
                     args = (t(logit, dev), t(emb, dev), unc, pur, norm, t(gt, dev))
                     kw = dict(size=3, K=7, active=None if a is None else t(a, dev))
                     new = score_maps(*args, **kw)
-                    old = _with_env({"HALO_NO_FUSE_TAIL": "1"}, lambda: score_maps(*args, **kw))
+                    old = score_maps(*args, out=_offset_copy(torch.zeros_like(new[0])), **kw)
                     for x, y in zip(new, old):
                         assert bits_equal(x.cpu().numpy(), y.cpu().numpy()), (H, W, dt, unc, pur, norm, a is None)
                     for b in range(2):
@@ -1827,8 +1845,9 @@ def test_fused_tail_equals_the_round2_tail_bitwise(dev):
 
 def test_feature_kernel_chunk_map_is_invisible(dev):
     """k_feat_reduce deals its 2 KiB pixel chunks to workgroups XCD-contiguously (granule 256 chunks, halved to fit small maps,
-    plain map past the last whole group): the three maps are the same bits as with the plain map (HALO_FEAT_XCD_GRANULE=-1),
-    with odd granules, and as the oracle's -- chunk counts that are / are not multiples of 8 granules, a partial last chunk."""
+    plain map past the last whole group): the three maps are the same bits as the oracle's and as those of the same embedding at
+    an unaligned address (one pixel per lane: twice the chunks, another granule or the plain map) -- chunk counts that are / are
+    not multiples of 8 granules, a partial last chunk."""
     from halo_amd.core.active.floating_region import score_maps
     from oracle import halo_oracle as ho
     rng = np.random.default_rng(404)
@@ -1838,10 +1857,9 @@ def test_feature_kernel_chunk_map_is_invisible(dev):
             emb = (rng.standard_normal((2, C, H, W)) * 0.05).astype(dt)
             args = (t(logit, dev), t(emb, dev), "entropy", "radius", True, None)
             new = score_maps(*args, size=3)
-            for g in ("-1", "3", "1", "1000000"):
-                old = _with_env({"HALO_FEAT_XCD_GRANULE": g}, lambda: score_maps(*args, size=3))
-                for x, y in zip(new, old):
-                    assert bits_equal(x.cpu().numpy(), y.cpu().numpy()), (H, W, dt, g)
+            old = score_maps(args[0], _offset_copy(args[1]), *args[2:], size=3)
+            for x, y in zip(new, old):
+                assert bits_equal(x.cpu().numpy(), y.cpu().numpy()), (H, W, dt)
             if H * W <= 128 * 1024:
                 so, io, uo = ho.floating_region_score(logit[1:2], emb[1:2], "entropy", "radius", True, None, size=3, purity_type="radius")
                 assert bits_equal(new[0][1].cpu().numpy(), so) and bits_equal(new[1][1].cpu().numpy(), io) and bits_equal(new[2][1].cpu().numpy(), uo)
@@ -2032,13 +2050,16 @@ def _torch_local_consistent(x, label, kl):
 def test_training_losses_ragged_shapes_and_many_classes(dev):
     """The loss kernels' other arms against a plain torch statement of the same modules under autograd: pixel counts that are not a
     multiple of four (scalar softmax), more than 20 classes (two-pass backward), one class, a single row / column, a label map
-    with no boundary at all in one image, ignore labels; NegativeLearningLoss on unaligned views and lengths n % 4 != 0."""
+    with no boundary at all in one image, ignore labels, an image taller than the strip-walking forward's grid serves (8 x 65535
+    rows: the one-pixel-per-thread forward); NegativeLearningLoss on unaligned views and lengths n % 4 != 0."""
     from halo_amd.core.loss import LocalConsistentLoss, NegativeLearningLoss
     g = torch.Generator(device="cpu").manual_seed(31)
-    for (B, O, h, w) in ((2, 19, 24, 40), (1, 19, 7, 9), (2, 21, 6, 10), (1, 3, 1, 17), (1, 5, 13, 1), (2, 1, 5, 6), (1, 20, 16, 12)):
-        x0 = (torch.randn((B, O, h, w), generator=g) * 2.0).to(dev)
-        label = torch.randint(0, max(2, O), (B, (h + 3) // 4, (w + 3) // 4), generator=g).repeat_interleave(4, 1).repeat_interleave(4, 2)[:, :h, :w].contiguous()
-        label[torch.rand((B, h, w), generator=g) < 0.1] = 255
+    for (B, O, h, w) in ((2, 19, 24, 40), (1, 19, 7, 9), (2, 21, 6, 10), (1, 3, 1, 17), (1, 5, 13, 1), (2, 1, 5, 6), (1, 20, 16, 12),
+                         (1, 3, 8 * 65535 + 9, 2)):
+        gs = g if h <= 8 * 65535 else torch.Generator(device="cpu").manual_seed(h)      # (the tall image draws from a stream of its own)
+        x0 = (torch.randn((B, O, h, w), generator=gs) * 2.0).to(dev)
+        label = torch.randint(0, max(2, O), (B, (h + 3) // 4, (w + 3) // 4), generator=gs).repeat_interleave(4, 1).repeat_interleave(4, 2)[:, :h, :w].contiguous()
+        label[torch.rand((B, h, w), generator=gs) < 0.1] = 255
         if B > 1:
             label[1] = 3                                              # no boundary in the second image
         label = label.to(dev)
@@ -2046,16 +2067,14 @@ def test_training_losses_ragged_shapes_and_many_classes(dev):
             xb = x0.clone().requires_grad_(True)
             lb = _torch_local_consistent(xb, label, lt == "kl")
             gb = None if bool(torch.isnan(lb)) else torch.autograd.grad(lb, xb)[0]
-            for env in ({}, {"HALO_LCL_PLAIN": "1"}):          # the strip-walking forward (default) and the one-pixel-per-thread forward
-                with _env_set(env):
-                    xa = x0.clone().requires_grad_(True)
-                    la = LocalConsistentLoss(O, lt)(xa, label)
-                    if gb is None:
-                        assert bool(torch.isnan(la))
-                        continue
-                    assert abs(la.item() - lb.item()) < 3e-6 * max(1.0, abs(lb.item())), (B, O, h, w, lt, env, la.item(), lb.item())
-                    (ga,) = torch.autograd.grad(la, xa)
-                    assert float((ga - gb).abs().max()) < 3e-5 * float(gb.abs().max()) + 1e-9, (B, O, h, w, lt, env)
+            xa = x0.clone().requires_grad_(True)
+            la = LocalConsistentLoss(O, lt)(xa, label)
+            if gb is None:
+                assert bool(torch.isnan(la))
+                continue
+            assert abs(la.item() - lb.item()) < 3e-6 * max(1.0, abs(lb.item())), (B, O, h, w, lt, la.item(), lb.item())
+            (ga,) = torch.autograd.grad(la, xa)
+            assert float((ga - gb).abs().max()) < 3e-5 * float(gb.abs().max()) + 1e-9, (B, O, h, w, lt)
     for n, off in ((1000, 0), (1003, 0), (1001, 1), (5, 3), (4096, 2)):
         buf = torch.rand(n + off + 8, generator=g).to(dev) * 0.2
         pa, pb = buf[off:off + n].clone().requires_grad_(True), buf[off:off + n].clone().requires_grad_(True)
@@ -2448,9 +2467,10 @@ def test_bench_dump_outputs_are_the_last_timed_steps_and_repeat(dev, tmp_path):
 
 
 def test_head_kernel_variants_agree_bitwise(dev):
-    """Round-2 kernels of the head tail against the round-1 kernels they replace (kept behind A/B switches) and the
-    oracle: expmap0+project through an LDS tile (single read, hoisted exact division) vs the two-pass plane walk;
-    bilinear with LDS-staged taps vs global gathers vs one element per thread."""
+    """Round-2 kernels of the head tail against the round-1 kernels they replace and the oracle: expmap0+project in registers or
+    through an LDS tile (single read, hoisted exact division) vs the two-pass plane walk (which serves an input that is not 8-byte
+    aligned); bilinear with LDS-staged taps, global gathers (float32 x >= 3, wide source windows) and one element per thread (more
+    than 65535 output rows), each bit for bit with the oracle."""
     from halo_amd.core.utils.hyperbolic import HyperMapper, bilinear_align_corners
     from oracle import halo_oracle as ho
     rng = np.random.default_rng(61)
@@ -2464,40 +2484,40 @@ def test_head_kernel_variants_agree_bitwise(dev):
             if h > 2:
                 z[-1, :, 2, 3] = 3.0e18                              # huge finite values
             a = m.expmap(t(z, dev), dim=1).cpu().numpy()
-            b = _with_env({"HALO_EXPMAP_PLANES": "1"}, lambda: m.expmap(t(z, dev), dim=1).cpu().numpy())
+            b = m.expmap(_offset_copy(t(z, dev)), dim=1).cpu().numpy()
             assert bits_equal(a, b), (c, C, h, w)
             assert max_abs_diff(a, ho.expmap(z, c, dim=1)) < 1e-14
             n = np.sqrt((a * a).sum(axis=1))
             assert n.max() <= (1 - 1e-5) / math.sqrt(c) * (1 + 1e-12)
     for dt in (np.float64, np.float32):
         for (planes, hin, hout) in ((5, (16, 32), (64, 128)), (3, (40, 80), (64, 128)), (2, (10, 20), (64, 128)), (4, (23, 37), (50, 77)),
-                                    (1, (64, 128), (64, 128)), (7, (5, 7), (96, 130)), (2, (64, 96), (16, 24)), (9, (33, 65), (129, 1030))):
+                                    (1, (64, 128), (64, 128)), (7, (5, 7), (96, 130)), (2, (64, 96), (16, 24)), (9, (33, 65), (129, 1030)),
+                                    (2, (7, 3), (65600, 5))):
             src = rng.standard_normal((1, planes) + hin).astype(dt)
             a = bilinear_align_corners(t(src, dev), hout).cpu().numpy()
-            b = _with_env({"HALO_BILINEAR_ROWS": "1"}, lambda: bilinear_align_corners(t(src, dev), hout).cpu().numpy())
-            c_ = _with_env({"HALO_BILINEAR_FLAT": "1"}, lambda: bilinear_align_corners(t(src, dev), hout).cpu().numpy())
-            assert bits_equal(a, b) and bits_equal(a, c_), (dt, planes, hin, hout)
             assert bits_equal(a, ho.bilinear(src, hout)), (dt, planes, hin, hout)
 
 
 def test_region_impurity_lds_tile_equals_generic_kernel(dev):
-    """The 3x3 sliding-window histogram on an LDS label tile vs the generic global re-scan kernel (A/B switch) and
-    the oracle, for label maps with many / few distinct classes, odd sizes, 1-pixel-wide maps."""
+    """The 3x3 sliding-window histogram on an LDS label tile and the generic global re-scan kernel (which serves the other padding
+    modes) against the oracle, for label maps with many / few distinct classes, odd sizes, 1-pixel-wide maps."""
     from halo_amd.core.active.floating_region import FloatingRegionScore
     from oracle import halo_oracle as ho
     rng = np.random.default_rng(71)
     for (H, W, K) in ((64, 128, 19), (37, 53, 100), (1, 70, 19), (90, 1, 7), (16, 64, 2), (130, 67, 19)):
         f = FloatingRegionScore(in_channels=K, size=3, purity_type="ripu")
+        fg = FloatingRegionScore(in_channels=K, size=3, purity_type="ripu", padding_mode="replicate")
         for kind in ("noise", "blobs"):
             lab = rng.integers(0, K, (H, W))
             if kind == "blobs":
                 lab = (ho.bilinear(rng.standard_normal((1, max(1, H // 8) + 1, max(1, W // 8) + 1)), (H, W))[0] * 2).astype(np.int64) % K
             lab = lab.astype(np.int64)
             imp, cnt = f.compute_region_impurity(t(lab, dev), K)
-            imp_g, cnt_g = _with_env({"HALO_IMPURITY_GENERIC": "1"}, lambda: f.compute_region_impurity(t(lab, dev), K))
-            assert bits_equal(imp.cpu().numpy(), imp_g.cpu().numpy()) and bits_equal(cnt.cpu().numpy(), cnt_g.cpu().numpy()), (H, W, K, kind)
+            imp_g, cnt_g = fg.compute_region_impurity(t(lab, dev), K)
             want_i, want_c = ho.region_impurity(lab, K, 3)
             assert bits_equal(imp.cpu().numpy(), want_i) and np.array_equal(cnt.cpu().numpy(), want_c), (H, W, K, kind)
+            want_i, want_c = ho.region_impurity(lab, K, 3, padding_mode="replicate")
+            assert bits_equal(imp_g.cpu().numpy(), want_i) and np.array_equal(cnt_g.cpu().numpy(), want_c), (H, W, K, kind, "replicate")
 
 
 def test_v2_head_class_end_to_end_against_reference_vectors(golden, dev):
@@ -2732,14 +2752,16 @@ def test_device_resize_is_torchs_cpu_interpolate_bit_for_bit(dev, dtype, shape):
     assert got.dtype == want.dtype and torch.equal(got, want)
 
 
-@pytest.mark.parametrize("C,hf,wf,H,W", [(40, 160, 320, 1024, 2048), (22, 256, 512, 1024, 2048), (17, 64, 128, 256, 512), (9, 22, 44, 64, 128), (12, 40, 64, 150, 250),
+@pytest.mark.parametrize("C,hf,wf,H,W", [(40, 160, 320, 1024, 2048), (22, 256, 512, 1024, 2048), (19, 512, 1024, 1024, 2048), (19, 160, 640, 1024, 2048),
+                                          (17, 64, 128, 256, 512), (9, 22, 44, 64, 128), (12, 40, 64, 150, 250),
                                           (8, 16, 32, 100, 136), (5, 30, 50, 95, 190), (33, 12, 24, 80, 192)])
 def test_lowres_exact_mode_staging_variants_agree_bitwise(dev, C, hf, wf, H, W):
     """The exact low-res embedding pass has four statements of one arithmetic: LDS-DMA with a compile-time window geometry and 8
-    pixels per lane (default where a source row is at least 3 output rows tall; row codes of HALO_LR_CODES8, anything else takes
-    the in-kernel generic loop), the same with 4 pixels per lane (HALO_LR_PPT4=1), runtime strides (HALO_LR_NOFIXED=1) and
-    register staging (HALO_LR_NODMA=1).  Same bits from all of them -- at x6.4 and x4 at FULL size with a partial last chunk (the
-    race of round 4 -- NOTES.md -- only fired with a full chip of waves in flight), at a scale of exactly 1/3 (three-row runs,
+    pixels per lane (where a source row is at least 3 output rows tall and the window fits: x6.4, x4; row codes of HALO_LR_CODES8,
+    anything else takes the in-kernel generic loop), the same with 4 pixels per lane (windows only that fits: x6.4 rows by x3.2
+    columns, a scale of exactly 1/3 ... 0.3), runtime strides (wider windows: x2, x3) and register staging (an embedding that is
+    not 16-byte aligned: every geometry once more).  Same bits from all of them -- each at FULL size with a partial last chunk
+    (the race of round 4 -- NOTES.md -- only fired with a full chip of waves in flight), at a scale of exactly 1/3 (three-row runs,
     three steps inside a lane's 8 pixels), at heights that are no multiple of 32 and widths that are no multiple of 64 -- and
     the same bits as upsample-then-score."""
     from halo_amd.core.active.floating_region import score_maps, score_maps_lowres
@@ -2749,11 +2771,11 @@ def test_lowres_exact_mode_staging_variants_agree_bitwise(dev, C, hf, wf, H, W):
     emb_lr = ho.expmap((rng.standard_normal((2, C, hf, wf)) * 0.2).astype(np.float32), 1.0, dim=1)
     lg, em = t(rng.standard_normal((2, 19, hf, wf)).astype(np.float32), dev), t(emb_lr, dev)
     want = score_maps(bilinear_align_corners(lg, (H, W)), bilinear_align_corners(em, (H, W)), "entropy", "radius", True, None, size=3)
-    for env in ({}, {"HALO_LR_PPT4": "1"}, {"HALO_LR_NOFIXED": "1"}, {"HALO_LR_NODMA": "1"}):
-        got = _with_env(env, lambda: score_maps_lowres(lg, em, (H, W), "entropy", "radius", True, None, ksize=3, mode="exact"))
+    for aligned in (True, False):
+        got = score_maps_lowres(lg, em if aligned else _offset_copy(em), (H, W), "entropy", "radius", True, None, ksize=3, mode="exact")
         torch.cuda.synchronize()
         for x, y in zip(got, want):
-            assert bits_equal(x.cpu().numpy(), y.cpu().numpy()), env
+            assert bits_equal(x.cpu().numpy(), y.cpu().numpy()), aligned
 
 
 def test_the_visualize_wrong_call_pattern(dev, monkeypatch):

@@ -68,9 +68,6 @@ done
 [ -x $R/tools/micro/coissue ] || hipcc --offload-arch=gfx950 -O3 $R/tools/micro/coissue.hip -o $R/tools/micro/coissue
 run coissue.txt $R/tools/micro/coissue
 # ---- A/B tools (each ASSERTS that its variants agree bit for bit)
-run ab_feat_map.txt python3 $R/tools/ab_feat_map.py
-run ab_lowres_dma.txt python3 $R/tools/ab_lowres_dma.py
-run gram_ab.txt python3 $R/tools/ab_gram.py
 run ab_mlr_epilogue.txt python3 $R/tools/ab_mlr_epilogue.py
 # (the logarithm's table from LDS against a -DHALO_LOGF_LDS=0 build reading it from device memory; the variant library travels when it
 #  was built in the container: python -c "from halo_amd import _build; _build.FLAGS.append('-DHALO_LOGF_LDS=0'); _build._build_locked(False, objdir='/tmp/obj_nolds', so='halo_amd/csrc/variants/libhalo_hip_logf_global.so')")

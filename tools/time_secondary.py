@@ -1,7 +1,6 @@
 """Timing aid: the secondary kernels of the head tail at the shapes round 1 profiled (one MI355X):
 expmap0+project (float32 planes -> float64), bilinear align_corners resize, HyperMLR.  Prints ms and the
-achieved fraction of the 8 TB/s HBM spec from algorithmic bytes; set HALO_EXPMAP_PLANES=1 / HALO_BILINEAR_FLAT=1
-for the previous kernels (A/B)."""
+achieved fraction of the 8 TB/s HBM spec from algorithmic bytes."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,13 +23,9 @@ def t(fn, n=10):
 m = HyperMapper(1.0)
 for (C, h, w) in ((256, 256, 512), (64, 160, 320), (64, 640, 1280), (512, 256, 512)):
     z = torch.randn((1, C, h, w), device=dev) * 0.1
-    for env in ({}, {"HALO_EXPMAP_PLANES": "1"}):
-        os.environ.update(env)
-        ms = t(lambda: m.expmap(z, dim=1))
-        for k in env:
-            os.environ.pop(k)
-        by = z.numel() * (4 + 8)
-        print(f"expmap f32->f64 C={C} {h}x{w} {'two-pass' if env else 'LDS tile'}: {ms:.3f} ms  {by / ms / 1e6:.0f} GB/s  frac {by / ms / 1e6 / 8000:.2f}", flush=True)
+    ms = t(lambda: m.expmap(z, dim=1))
+    by = z.numel() * (4 + 8)
+    print(f"expmap f32->f64 C={C} {h}x{w}: {ms:.3f} ms  {by / ms / 1e6:.0f} GB/s  frac {by / ms / 1e6 / 8000:.2f}", flush=True)
     dst = torch.empty((1, C, h, w), device=dev, dtype=torch.float64)
     ms_copy = t(lambda: dst.copy_(z))
     print(f"   torch copy_ f32 -> f64 of the same tensor (read 4 B, write 8 B per element, no arithmetic): {ms_copy:.3f} ms  {z.numel() * 12 / ms_copy / 1e6:.0f} GB/s", flush=True)
@@ -38,13 +33,9 @@ for (C, h, w) in ((256, 256, 512), (64, 160, 320), (64, 640, 1280), (512, 256, 5
 for (dt, planes, hw_in, hw_out) in ((torch.float64, 256, (256, 512), (1024, 2048)), (torch.float32, 19, (256, 512), (1024, 2048)),
                                     (torch.float32, 19, (640, 1280), (1024, 2048)), (torch.float64, 64, (160, 320), (1024, 2048))):
     src = torch.randn((1, planes) + hw_in, device=dev, dtype=dt)
-    for env in ({}, {"HALO_BILINEAR_FLAT": "1"}):
-        os.environ.update(env)
-        ms = t(lambda: bilinear_align_corners(src, hw_out))
-        for k in env:
-            os.environ.pop(k)
-        by = (src.numel() + planes * hw_out[0] * hw_out[1]) * src.element_size()
-        print(f"bilinear {str(dt)[6:]} {planes}x{hw_in}->{hw_out} {'flat' if env else 'rows'}: {ms:.3f} ms  {by / ms / 1e6:.0f} GB/s  frac {by / ms / 1e6 / 8000:.2f}", flush=True)
+    ms = t(lambda: bilinear_align_corners(src, hw_out))
+    by = (src.numel() + planes * hw_out[0] * hw_out[1]) * src.element_size()
+    print(f"bilinear {str(dt)[6:]} {planes}x{hw_in}->{hw_out}: {ms:.3f} ms  {by / ms / 1e6:.0f} GB/s  frac {by / ms / 1e6 / 8000:.2f}", flush=True)
     # what a plain store stream of the same output gets on this box (the resize writes 16-40x what it reads)
     dst = torch.empty((1, planes) + hw_out, device=dev, dtype=dt)
     ms_fill = t(lambda: dst.fill_(1.0))
