@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(CSRC, "libhalo_hip.so")
-SOURCES = ["halo_api.hip", "halo_score.hip", "halo_select.hip", "halo_select_binned.hip", "halo_hyperbolic.hip", "halo_loss.hip", "halo_pool.hip", "halo_eval.hip"]
+SOURCES = ["halo_api.hip", "halo_score.hip", "halo_select.hip", "halo_select_binned.hip", "halo_hyperbolic.hip", "halo_loss.hip", "halo_pool.hip", "halo_eval.hip", "halo_train_loss.hip"]
 HOST_SO = os.path.join(CSRC, "libhalo_host.so")          # plain C host helpers (PNG writer of the persistence step), built with gcc
 HOST_SOURCES = ["halo_host.c"]
 HEADERS = ["halo_common.hpp", "halo_devmath.hpp", "halo_softmax.hpp", "halo_select_common.hpp", "halo_select_plan.hpp", os.path.join("..", "..", "include", "halo_hip.h")]
@@ -24,8 +24,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=o
 # halo_score.hip: no SLP vectorisation.  Packing the per-class float32 chains of the entropy code into v_pk_* saves 10 % of
 # its instructions but costs 40 VGPRs (operand pairs, constants held in registers): 116-120 instead of 79, i.e. 4 instead
 # of 6 waves per SIMD for the fused feature kernel, and the stand-alone logit kernel runs 8 % slower packed.
-# halo_eval.hip runs the same softmax statements (halo_softmax.hpp) and takes the same flag.
-EXTRA_FLAGS = {"halo_score.hip": ["-fno-slp-vectorize"], "halo_eval.hip": ["-fno-slp-vectorize"]}
+# halo_eval.hip and halo_train_loss.hip run the same softmax statements (halo_softmax.hpp) and take the same flag.
+EXTRA_FLAGS = {"halo_score.hip": ["-fno-slp-vectorize"], "halo_eval.hip": ["-fno-slp-vectorize"], "halo_train_loss.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():

@@ -16,6 +16,7 @@ UNC_ZEROS = 3
 PUR = {"ripu": 0, "oracle_ripu": 1, "hyper": 2, "none": 3, "radius": 4, "euc_norm": 5}
 E_UNSUPPORTED = -2
 SELECT = {"auto": 0, "serial": 1, "binned": 2}                      # HALO_SELECT_* of include/halo_hip.h
+LOSS_CE, LOSS_NL = 1, 2                                             # HALO_LOSS_*: terms of halo_upsampled_loss_*
 SWEEP_REASONS = ("done", "bad_values", "bin_overflow", "survivors", "exhausted", "not_run")      # HALO_SWEEP_*
 PAD = {"zeros": 0, "reflect": 1, "replicate": 2, "circular": 3}     # HALO_PAD_*: nn.Conv2d's padding_mode values
 FLAG_NORMALIZE = 1
@@ -70,6 +71,9 @@ SIGNATURES = {
     "halo_eval_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "halo_eval_confusion": (_int, [_vp, _i64, _int, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "halo_confusion_from_pred": (_int, [_vp, _int, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "halo_upsampled_loss_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "halo_upsampled_loss_fwd": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _dbl, _int, _vp, _vp, _sz, _vp]),
+    "halo_upsampled_loss_bwd": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _dbl, _int, _vp, _vp, _vp, _vp, _vp]),
     "halo_event_create": (_vp, []),
     "halo_event_record": (_int, [_vp, _vp]),
     "halo_event_elapsed_ms": (_int, [_vp, _vp, C.POINTER(C.c_float)]),
@@ -91,7 +95,7 @@ SIGNATURES = {
 
 # must equal HALO_ABI_VERSION of include/halo_hip.h; bumped whenever an exported signature changes, so a stale
 # library with the same symbol names but older argument lists is refused instead of being called with shifted arguments
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lock = threading.Lock()
 _handle = None

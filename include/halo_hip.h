@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 9
+#define HALO_ABI_VERSION 10
 
 enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4 };
 
@@ -339,6 +339,33 @@ int halo_eval_confusion(const float *logit, int64_t logit_bstride, int views, in
                         void *workspace, size_t workspace_bytes, void *stream);
 int halo_confusion_from_pred(const void *pred, int pred_dtype, const void *label, int label_dtype, int64_t K, int64_t H, int64_t W,
                              int64_t B, int64_t ignore_index, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- training criterion from low-resolution logits (ABI 10): BaseLearner.forward(size=input_size) -> torch.softmax ->
+ *  nn.CrossEntropyLoss(ignore_index) + NegativeLearningLoss(threshold), and their backward to the logits
+ *  (core/train_learners.py:224-243, 328-368, 404-463, 505-563; core/loss/negative_learning_loss.py:6-16) ----
+ *  logit (B, K, h, w) f32, image i at logit + i * logit_bstride; label (B, H, W) of label_dtype HALO_I64 / HALO_I32 / HALO_U8.
+ *  Per output pixel: bilinear upsampling to H x W (align_corners=True) and softmax, torch's CPU kernels bit for bit (as
+ *  halo_eval_confusion); the full-resolution maps are never written.  terms: HALO_LOSS_CE | HALO_LOSS_NL.
+ *  halo_upsampled_loss_fwd OVERWRITES sums[5] (f64, device) = {ce_sum, ce_count, nl_sum, nl_count, bad_label_count}:
+ *    ce over the labels y with 0 <= y < K and y != ignore_index, -log_softmax[y]; nl over the (pixel, class) pairs with
+ *    p < (float)threshold, -log((1 - p) + 1e-6); bad_label_count = labels neither ignore_index nor in [0, K) (never used as an
+ *    index).  The counts are computed whatever `terms` says; a term that is off leaves its sum 0.  The caller forms
+ *    ce = ce_sum / ce_count (NaN over no label, as torch) and nl = nl_sum / nl_count.
+ *  halo_upsampled_loss_bwd WRITES grad_logit (B, K, h, w) f32 dense: the adjoint of the resize applied to
+ *    d_k = g_ce/ce_count (p_k - [k = y]) [labelled] + g_nl/nl_count p_k (q_k - sum_c q_c p_c),  q_c = [p_c < thr] / ((1 - p_c) + 1e-6),
+ *    with sums from the forward of the same inputs and g_ce / g_nl device scalars f32 (NULL = no upstream gradient); a term
+ *    whose count is 0 contributes 0.  Gather order fixed, no atomics: repeated calls give identical bits.
+ *  Both reduce in a fixed order without atomics.  HALO_E_UNSUPPORTED: K > 1024, H < h or W < w (torch also interpolates
+ *  down; this path upsamples only), other label dtypes; HALO_E_ARG: an empty shape; HALO_E_WORKSPACE: a short workspace.
+ *  workspace (fwd only): halo_upsampled_loss_workspace_bytes(B, K, H, W) (five f64 partials per 1024 output pixels). */
+enum { HALO_LOSS_CE = 1, HALO_LOSS_NL = 2 };
+size_t halo_upsampled_loss_workspace_bytes(int64_t B, int64_t K, int64_t H, int64_t W);
+int halo_upsampled_loss_fwd(const float *logit, int64_t logit_bstride, int64_t B, int64_t K, int64_t h, int64_t w, const void *label,
+                            int label_dtype, int64_t H, int64_t W, int64_t ignore_index, double threshold, int terms, double *sums,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int halo_upsampled_loss_bwd(const float *logit, int64_t logit_bstride, int64_t B, int64_t K, int64_t h, int64_t w, const void *label,
+                            int label_dtype, int64_t H, int64_t W, int64_t ignore_index, double threshold, int terms,
+                            const double *sums, const float *g_ce, const float *g_nl, float *grad_logit, void *stream);
 
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
