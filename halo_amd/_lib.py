@@ -74,6 +74,11 @@ SIGNATURES = {
     "halo_upsampled_loss_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "halo_upsampled_loss_fwd": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _dbl, _int, _vp, _vp, _sz, _vp]),
     "halo_upsampled_loss_bwd": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _dbl, _int, _vp, _vp, _vp, _vp, _vp]),
+    "halo_hfr_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "halo_hfr_fwd_stats": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "halo_hfr_fwd_apply": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "halo_hfr_bwd_reduce": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "halo_hfr_bwd_apply": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "halo_event_create": (_vp, []),
     "halo_event_record": (_int, [_vp, _vp]),
     "halo_event_elapsed_ms": (_int, [_vp, _vp, C.POINTER(C.c_float)]),

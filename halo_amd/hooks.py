@@ -271,3 +271,37 @@ def use_fused_training_losses(learner_cls):
     learner_cls._reference_training_step = _inherited(learner_cls, "training_step")
     learner_cls.training_step = fused_training_step
     return learner_cls
+
+
+# ---------------------------------------------------------------- HFR weighted normalisation of the v3+ head
+# With cfg.MODEL.HFR the DeepLab-v3+ hyperbolic head runs the `wn_mlp` weighted normalisation between conv_reduce and
+# mapper.expmap (core/models/classifier.py:529-550), as torch statements.  `use_fused_feature_reweighting(head_cls)` binds
+# `fused_v3plus_hyper_forward`: halo_amd.core.models.classifier.v3plus_hyper_forward with that statement replaced by
+# halo_amd.hfr.weighted_normalize (halo_hfr.hip, which keeps the torch statement outside its envelope).  The previous forward is
+# kept as `_unfused_forward`.  Neither install() nor the existing forward changes.
+
+def fused_v3plus_hyper_forward(self, x, size=None):
+    from .core.models.classifier import _tail_modules, hyper_head_tail
+    from .hfr import weighted_normalize
+    low, top = x["low"], x["out"]
+    pyramid = [branch(top) for branch in self.parallel_branches]
+    pooled = self.global_branch(top)
+    pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+    fused = self.bottleneck(torch.cat(pyramid, dim=1))
+    fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
+    dec = self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
+    dec = self.conv_reduce(dec)
+    if getattr(self, "wn_mlp", None) is not None:
+        dec = weighted_normalize(dec, self.wn_mlp)
+    mapper, seg = _tail_modules(self)
+    return hyper_head_tail(dec, mapper, seg, size=size, resize_embed=False)
+
+
+def use_fused_feature_reweighting(head_cls):
+    """Bind fused_v3plus_hyper_forward on a DeepLab-v3+ hyperbolic head class (the reference's DepthwiseSeparableASPP_Hyper or
+    halo_amd's drop-in).  Returns the class; the forward it replaced is kept as `_unfused_forward`."""
+    if head_cls.__dict__.get("forward") is fused_v3plus_hyper_forward:
+        return head_cls
+    head_cls._unfused_forward = _inherited(head_cls, "forward")
+    head_cls.forward = fused_v3plus_hyper_forward
+    return head_cls

@@ -367,6 +367,34 @@ int halo_upsampled_loss_bwd(const float *logit, int64_t logit_bstride, int64_t B
                             int label_dtype, int64_t H, int64_t W, int64_t ignore_index, double threshold, int terms,
                             const double *sums, const float *g_ce, const float *g_nl, float *grad_logit, void *stream);
 
+/* ---- HFR weighted normalisation of the DeepLab-v3+ hyperbolic head, forward and backward (core/models/classifier.py:529-550) ----
+ *  x (B, C, P) f32 dense (the conv_reduce output, P = h * w); wn_mlp = Linear(C, C) [W1 (C, C), b1] -> BatchNorm1d(C) [gamma, beta,
+ *  NULL = not affine] -> ReLU -> Linear(C, C) [W2, b2]; every parameter f32 dense on the device.  C <= 256 (C = 64 templated).
+ *    h_p = W1 x_p + b1, z = BN(h), w_b = W2 mean_p relu(z_p) + b2, wc = clamp(w, min=1e-5), y = (x / max(||x_bc||_2, 1e-12)) * wc.
+ *  One workspace of halo_hfr_workspace_bytes(B, C, P) serves a forward and the backward of the same inputs: it carries the
+ *  forward's state to the backward, so the caller keeps it between the two.
+ *  halo_hfr_fwd_stats WRITES stats (C, 3) f64 = (count, mean, M2) of h per channel over the B * P rows.  Rows of several ranks
+ *    may be merged (Chan's formula) by the caller before:
+ *  halo_hfr_fwd_apply WRITES y (B, C, P) f32.  stats = the batch statistics (training), then running_mean / running_var (f32,
+ *    NULL = not tracked) take F.batch_norm's update with factor `momentum` and the unbiased variance; stats = NULL: the running
+ *    statistics normalise (evaluation) and are not changed.
+ *  halo_hfr_bwd_reduce (g = dL/dy) WRITES g_W2, g_b2, g_gamma, g_beta (NULL when not affine; this call's rows only) and
+ *    gsums (C, 2) f64 = (sum g_z, sum g_z zhat) per channel.  Ranks may all-reduce gsums before:
+ *  halo_hfr_bwd_apply WRITES g_x (B, C, P), g_W1 (C, C), g_b1 (C).
+ *  Every reduction runs in a fixed order without atomics: repeated calls give identical bits.  HALO_E_UNSUPPORTED: C > 256,
+ *  B > 65535 or P > 65535 * 1024; HALO_E_ARG: an empty shape or a missing pointer; HALO_E_WORKSPACE: a short workspace. */
+size_t halo_hfr_workspace_bytes(int64_t B, int64_t C, int64_t P);
+int halo_hfr_fwd_stats(const float *x, int64_t B, int64_t C, int64_t P, const float *W1, const float *b1, double *stats, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int halo_hfr_fwd_apply(const float *x, int64_t B, int64_t C, int64_t P, const float *W1, const float *b1, const double *stats,
+                       float *running_mean, float *running_var, double momentum, double eps, const float *gamma, const float *beta,
+                       const float *W2, const float *b2, float *y, void *workspace, size_t workspace_bytes, void *stream);
+int halo_hfr_bwd_reduce(const float *x, int64_t B, int64_t C, int64_t P, const float *W2, const float *g, float *g_W2, float *g_b2,
+                        float *g_gamma, float *g_beta, double *gsums, void *workspace, size_t workspace_bytes, void *stream);
+int halo_hfr_bwd_apply(const float *x, int64_t B, int64_t C, int64_t P, const float *W1, const float *b1, const float *gamma,
+                       const float *g, const double *gsums, float *g_x, float *g_W1, float *g_b1, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
 int halo_event_record(void *event, void *stream);
