@@ -26,18 +26,24 @@ from ..configs import cfg
 from ..utils.hyperbolic import HyperMapper, HyperMLR, bilinear_align_corners, head_tail_fused
 
 
-def hyper_head_tail(feat, mapper: HyperMapper, conv_seg: HyperMLR, size=None, resize_embed=False):
+def hyper_head_tail(feat, mapper: HyperMapper, conv_seg: HyperMLR, size=None, resize_embed=False, resize=None):
     """feat (B,C,h,w) float32 from conv_reduce / the ASPP sum -> (out float32, embed float64).
 
     resize_embed=False: DeepLab-v3+ tail (classifier.py:552-558); True: DeepLab-v2 tail, which also
-    resizes the embedding (classifier.py:375-377)."""
+    resizes the embedding (classifier.py:375-377).  resize: None (default) resizes with F.interpolate under training; a
+    callable (x, size) -> resized x replaces it there (halo_amd.resize.resize_or_interpolate for a head class marked with
+    halo_amd.hooks.use_device_resize: the HIP resize with its atomic-free backward)."""
     training = torch.is_grad_enabled() and (feat.requires_grad or conv_seg.P_MLR.requires_grad)
     if training:
-        # expmap and HyperMLR carry HIP backward kernels; the resize stays on F.interpolate, which autograd
-        # already differentiates (it is outside the kernels' scope under training)
+        # expmap and HyperMLR carry HIP backward kernels; by default the resize stays on F.interpolate, which autograd
+        # already differentiates; `resize` (see above) puts it on halo_amd.resize instead
         embed = mapper.expmap(feat, dim=1)
         out = conv_seg._hyper_logits(embed, out_dtype=torch.float32)      # = conv_seg(embed).float(), the cast fused into the kernel's store
-        if size is not None:
+        if size is not None and resize is not None:
+            out = resize(out, size)
+            if resize_embed:
+                embed = resize(embed, size)
+        elif size is not None:
             out = F.interpolate(out, size=size, mode="bilinear", align_corners=True)
             if resize_embed:
                 embed = F.interpolate(embed, size=size, mode="bilinear", align_corners=True)
@@ -77,6 +83,22 @@ def _tail_modules(head):
     return tail
 
 
+def device_resize(head_or_learner):
+    """halo_amd.resize.resize_or_interpolate when the instance's class is marked by halo_amd.hooks.use_device_resize, else None"""
+    if not getattr(type(head_or_learner), "_halo_device_resize", False):
+        return None
+    from ...resize import resize_or_interpolate
+    return resize_or_interpolate
+
+
+def broadcast_or_resize(pooled, size, resize):
+    """The global-pooling branch under the switch: align_corners=True of a single cell returns that cell exactly, so a 1 x 1
+    map is broadcast (expand's backward is torch's ordinary, deterministic sum); any other map goes through `resize`."""
+    if tuple(pooled.shape[2:]) == (1, 1):
+        return pooled.expand(-1, -1, int(size[0]), int(size[1]))
+    return resize(pooled, size)
+
+
 def v2_hyper_forward(self, x, size=None):
     """forward of ASPP_Classifier_V2_Hyper (classifier.py:364-379): sum of the dilated 3x3 branches, HIP tail;
     DeepLab-v2 resizes the logits AND the embedding."""
@@ -86,7 +108,7 @@ def v2_hyper_forward(self, x, size=None):
     for conv in branches:
         embed = embed + conv(feat)
     mapper, seg = _tail_modules(self)
-    return hyper_head_tail(embed, mapper, seg, size=size, resize_embed=True)
+    return hyper_head_tail(embed, mapper, seg, size=size, resize_embed=True, resize=device_resize(self))
 
 
 def v3plus_hyper_forward(self, x, size=None):
@@ -95,9 +117,14 @@ def v3plus_hyper_forward(self, x, size=None):
     low, top = x["low"], x["out"]
     pyramid = [branch(top) for branch in self.parallel_branches]
     pooled = self.global_branch(top)
-    pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
-    fused = self.bottleneck(torch.cat(pyramid, dim=1))
-    fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
+    resize = device_resize(self)
+    if resize is None:
+        pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+        fused = self.bottleneck(torch.cat(pyramid, dim=1))
+        fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
+    else:
+        pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
+        fused = resize(self.bottleneck(torch.cat(pyramid, dim=1)), low.shape[2:])
     dec = self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
     dec = self.conv_reduce(dec)
     if getattr(self, "wn_mlp", None) is not None:                      # classifier.py:531-550
@@ -106,7 +133,7 @@ def v3plus_hyper_forward(self, x, size=None):
         weights = weights.clamp(min=1e-5).view(b, ch, 1, 1)
         dec = F.normalize(dec.reshape(b, ch, h * w), dim=-1).reshape(b, ch, h, w) * weights
     mapper, seg = _tail_modules(self)
-    return hyper_head_tail(dec, mapper, seg, size=size, resize_embed=False)
+    return hyper_head_tail(dec, mapper, seg, size=size, resize_embed=False, resize=resize)
 
 
 class ASPP_Classifier_V2_Hyper(nn.Module):

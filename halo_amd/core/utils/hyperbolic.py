@@ -416,7 +416,8 @@ class HyperMetrics(object):
 
 def bilinear_align_corners(x, size):
     """F.interpolate(x, size, mode='bilinear', align_corners=True) for float32/float64 NCHW
-    (core/active/build.py:123-125,133-135; classifier.py:375-377,556-557)."""
+    (core/active/build.py:123-125,133-135; classifier.py:375-377,556-557).  Inference-only: it refuses an input that requires a
+    gradient.  halo_amd.resize.bilinear_resize is the same forward as an autograd function with a HIP backward."""
     _no_grad_only(x)
     dev = _lib.require_device(x)
     x = x.contiguous()

@@ -187,6 +187,7 @@ def _finish_step(self, optimizers, loss, batch_idx):
 
 
 def fused_training_step(self, batch, batch_idx):
+    from .core.models.classifier import device_resize
     from .training import upsampled_losses
     proto = _training_protocol(type(self))
     if proto is None:
@@ -251,7 +252,11 @@ def fused_training_step(self, batch, batch_idx):
         loss += loss_sup_tgt
         _log(self, 'loss_sup_tgt', loss_sup_tgt)
     if self.cfg.SOLVER.CONSISTENT_LOSS > 0:
-        src_out = F.interpolate(src_lg, size=src_input.shape[-2:], mode="bilinear", align_corners=True)
+        resize = device_resize(self)                  # use_device_resize(learner_cls): the HIP resize with its atomic-free backward
+        if resize is None:
+            src_out = F.interpolate(src_lg, size=src_input.shape[-2:], mode="bilinear", align_corners=True)
+        else:
+            src_out = resize(src_lg, src_input.shape[-2:])
         consistency_loss = self.local_consistent_loss(src_out, src_label) * self.cfg.SOLVER.CONSISTENT_LOSS
         loss += consistency_loss
         _log(self, 'consistency_loss', consistency_loss)
@@ -281,20 +286,25 @@ def use_fused_training_losses(learner_cls):
 # kept as `_unfused_forward`.  Neither install() nor the existing forward changes.
 
 def fused_v3plus_hyper_forward(self, x, size=None):
-    from .core.models.classifier import _tail_modules, hyper_head_tail
+    from .core.models.classifier import _tail_modules, broadcast_or_resize, device_resize, hyper_head_tail
     from .hfr import weighted_normalize
     low, top = x["low"], x["out"]
     pyramid = [branch(top) for branch in self.parallel_branches]
     pooled = self.global_branch(top)
-    pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
-    fused = self.bottleneck(torch.cat(pyramid, dim=1))
-    fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
+    resize = device_resize(self)
+    if resize is None:
+        pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+        fused = self.bottleneck(torch.cat(pyramid, dim=1))
+        fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
+    else:
+        pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
+        fused = resize(self.bottleneck(torch.cat(pyramid, dim=1)), low.shape[2:])
     dec = self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
     dec = self.conv_reduce(dec)
     if getattr(self, "wn_mlp", None) is not None:
         dec = weighted_normalize(dec, self.wn_mlp)
     mapper, seg = _tail_modules(self)
-    return hyper_head_tail(dec, mapper, seg, size=size, resize_embed=False)
+    return hyper_head_tail(dec, mapper, seg, size=size, resize_embed=False, resize=resize)
 
 
 def use_fused_feature_reweighting(head_cls):
@@ -305,3 +315,27 @@ def use_fused_feature_reweighting(head_cls):
     head_cls._unfused_forward = _inherited(head_cls, "forward")
     head_cls.forward = fused_v3plus_hyper_forward
     return head_cls
+
+
+# ---------------------------------------------------------------- resizes of the training paths on the device operator
+# Under training every align_corners resize of the package's forwards is an F.interpolate, whose device backward scatters float
+# atomic adds: the one source of run-to-run differences in a step's gradients.  `use_device_resize(cls)` marks a head class (one that
+# carries v2_hyper_forward, v3plus_hyper_forward or fused_v3plus_hyper_forward) or a learner class (fused_training_step's
+# LocalConsistentLoss input): marked classes resize through halo_amd.resize.resize_or_interpolate -- halo_bilinear_upsample forward,
+# its gather adjoint backward -- and broadcast the v3+ head's 1 x 1 global-pooling branch.  Nothing changes for an unmarked class.
+
+def _package_forwards():
+    from .core.models.classifier import v2_hyper_forward, v3plus_hyper_forward
+    return (v2_hyper_forward, v3plus_hyper_forward, fused_v3plus_hyper_forward)
+
+
+def use_device_resize(cls):
+    """Mark a head class or a learner class so that its training-path resizes run on halo_amd.resize.  Returns the class.
+    Composes with the other hooks in either order (the mark is a class attribute, the forwards read it when they run)."""
+    if not isinstance(cls, type):
+        raise TypeError("use_device_resize: expected a class, got %r" % (cls,))
+    if _training_protocol(cls) is None and not any(_inherited(cls, "forward") is f for f in _package_forwards()):
+        raise TypeError("use_device_resize: %s is neither a learner (%s) nor a head class that carries one of halo_amd's forwards; "
+                        "bind one first with halo_amd.install() or use_fused_feature_reweighting" % (cls.__name__, ", ".join(_PROTOCOLS)))
+    cls._halo_device_resize = True
+    return cls

@@ -121,6 +121,14 @@ int halo_hypermlr_backward(const double *x, const double *P, const double *A, co
 int halo_bilinear_upsample(const void *src, void *dst, int dtype, int64_t planes, int64_t h, int64_t w,
                            int64_t H, int64_t W, void *stream);
 
+/* The adjoint of that resize (its backward under autograd): grad_out planes x (H,W) -> WRITES grad_in planes x (h,w), both dense,
+ * dtype F32|F64, H >= h and W >= w (anything else: HALO_E_ARG, nothing launched).
+ *   grad_in[p,i,j] = sum_Y sum_X wy(Y,i) wx(X,j) grad_out[p,Y,X],  wy(Y,i) = [i0(Y) == i] l0(Y) + [i1(Y) == i] l1(Y)
+ * with the forward's taps and weights in the operand dtype.  A gather: no atomics, every grad_in element summed by one thread in
+ * a fixed order (ascending X inside a row, rows in ascending Y), so repeated calls give identical bits.  No workspace. */
+int halo_bilinear_upsample_bwd(const void *grad_out, void *grad_in, int dtype, int64_t planes, int64_t h, int64_t w,
+                               int64_t H, int64_t W, void *stream);
+
 /* ---- scoring: FloatingRegionScore.forward (core/active/floating_region.py:129-217) ----
  *
  * logit (B,O,H,W) f32; feat = decoder_out (B,C,H,W) f64|f32, needed for pur HYPER/RADIUS/EUC_NORM
