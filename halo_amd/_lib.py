@@ -80,6 +80,10 @@ SIGNATURES = {
     "halo_hfr_fwd_apply": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "halo_hfr_bwd_reduce": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "halo_hfr_bwd_apply": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "halo_dwconv_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "halo_dwconv3x3_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "halo_dwconv3x3_affine_relu_bwd_data": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "halo_dwconv3x3_affine_relu_bwd_weight": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
     "halo_event_create": (_vp, []),
     "halo_event_record": (_int, [_vp, _vp]),
     "halo_event_elapsed_ms": (_int, [_vp, _vp, C.POINTER(C.c_float)]),

@@ -1,0 +1,337 @@
+// The first half of a DepthwiseSeparableConv2d block with a frozen norm (core/models/classifier.py:78-81): depthwise 3 x 3
+// convolution (groups = C, dilation d, padding d, stride 1, no bias), per-channel affine, ReLU -- one read and one write.
+//
+//   pre[b,c,i,j] = (sum_{ky,kx} w[c,ky,kx] x[b,c, i + (ky-1) d, j + (kx-1) d]) * scale[c] + shift[c],   y = max(pre, 0)
+//   gp = g [y > 0] scale[c]                                   (float32, one rounding)
+//   g_x[b,c,p] = sum_k w[c,k] gp[b,c,p - k d]                 (a gather with the mirrored taps: one thread writes an element once)
+//   g_w[c,k]   = sum_{b,p} gp[b,c,p] x[b,c,p + k d]           (float64 products and sums, rounded to float32 once)
+//
+// Order of summation (every kernel, every route, whatever the tiling -- the bits depend on the operands and the shape alone):
+//   the 9-term sums run over the INPUT positions in ascending row, then ascending column: (i-d, j-d), (i-d, j), (i-d, j+d),
+//   (i, j-d), ... (i+d, j+d); the first product is rounded, every further term is one fma onto it; a tap outside the plane adds
+//   w * 0.  (For the forward that is ky, kx ascending; for g_x it is ky, kx descending.)  * scale and + shift are two roundings.
+//   g_w: a thread adds fma(gp, x, acc) in float64 over its rows in ascending order and, per row, its columns in ascending
+//   order; a block adds its threads by a fixed shuffle tree and its four waves in ascending order; k_dw_wsum adds the per-block
+//   rows of a channel in ascending (image, block) order.  No atomics anywhere.
+//
+// Tiling: no LDS.  A 3 x 3 tap set with dilation d touches rows i-d, i, i+d only, so the rows of a plane fall into d CHAINS
+// (r, r+d, r+2d, ...) that never read each other's rows.  A thread owns GW adjacent columns (4: 16-byte loads; 1: any W and any
+// alignment) of a chain segment of up to DW_L output rows and walks it top to bottom with a three-row window in registers:
+// every input row is loaded once per segment (three loads: the columns at -d, 0, +d; one load and two scalars for d = 1) and
+// serves three output rows.  Consecutive lanes take consecutive column groups, then the next chain, i.e. the next row: the loads
+// and stores of a wave are contiguous.  An 80 x 160 plane at d = 6 / 12 / 18 is 240 / 480 / 720 threads with no halo row at
+// all; a 160 x 320 plane at d = 1 is 10 bands of 16 rows with a one-row halo either side.  A block works inside one plane, so
+// w, scale and shift are block-uniform.
+#include "halo_common.hpp"
+
+namespace halo {
+
+constexpr int DW_TPB = 256;
+constexpr int DW_L = 16;                 // output rows of one chain segment
+constexpr int64_t DW_MAX_DIM = 1 << 24;  // H, W, d
+enum { DW_FWD = 0, DW_BWD = 1 };
+
+typedef float dw_f4 __attribute__((ext_vector_type(4)));
+typedef float dw_f4u __attribute__((ext_vector_type(4), aligned(4)));
+
+struct DwGeom {
+    int H, W, d, C;
+    int ngroups;      // column groups of GW columns per row
+    int nres;         // chains: min(d, H)
+    int bpp;          // blocks per plane
+    long long items;  // threads with work per plane: segments x chains x column groups
+};
+
+static DwGeom dw_geom(int64_t C, int64_t H, int64_t W, int64_t d, int gw)
+{
+    DwGeom G;
+    G.H = (int)H, G.W = (int)W, G.d = (int)d, G.C = (int)C;
+    G.ngroups = (int)(W / gw);
+    G.nres = (int)(d < H ? d : H);
+    const int64_t nseg = cdiv(cdiv(H, d), DW_L);
+    G.items = (long long)nseg * G.nres * G.ngroups;
+    G.bpp = (int)cdiv(G.items, DW_TPB);
+    return G;
+}
+
+// the operand a window is read from: x itself, or gp = g [y > 0] scale
+template <int MODE> struct DwSrc {
+    const float *a, *y;
+    float scale;
+    __device__ __forceinline__ float at(size_t o) const
+    {
+        if constexpr (MODE == DW_FWD) return a[o];
+        else return (y[o] > 0.0f ? a[o] : 0.0f) * scale;
+    }
+    template <typename V> __device__ __forceinline__ void at4(size_t o, float *out) const
+    {
+        const V va = *reinterpret_cast<const V *>(a + o);
+        if constexpr (MODE == DW_FWD) {
+            out[0] = va.x, out[1] = va.y, out[2] = va.z, out[3] = va.w;
+        } else {
+            const V vy = *reinterpret_cast<const V *>(y + o);
+            out[0] = (vy.x > 0.0f ? va.x : 0.0f) * scale, out[1] = (vy.y > 0.0f ? va.y : 0.0f) * scale;
+            out[2] = (vy.z > 0.0f ? va.z : 0.0f) * scale, out[3] = (vy.w > 0.0f ? va.w : 0.0f) * scale;
+        }
+    }
+    // the GW columns at c0 of row i (zeros outside the plane); ALIGNED: c0 is a multiple of 4 (16-byte loads)
+    template <int GW, bool ALIGNED> __device__ __forceinline__ void cols(float *out, int i, int c0, int H, int W) const
+    {
+        const bool row_in = i >= 0 && i < H;
+        const size_t o = (size_t)(row_in ? i : 0) * W;
+        if constexpr (GW == 4) {
+            if (row_in && c0 >= 0 && c0 + 4 <= W) {
+                if constexpr (ALIGNED) at4<dw_f4>(o + c0, out);
+                else at4<dw_f4u>(o + c0, out);
+                return;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < GW; ++e) out[e] = row_in && c0 + e >= 0 && c0 + e < W ? at(o + (c0 + e)) : 0.0f;
+    }
+    // win[kx * GW + e] = the operand at (i, c0 + (kx - 1) d + e)
+    template <int GW, bool D1> __device__ __forceinline__ void row(float *win, int i, int c0, int H, int W, int d) const
+    {
+        if constexpr (D1 && GW == 4) {
+            cols<4, true>(win + 4, i, c0, H, W);
+            const bool row_in = i >= 0 && i < H;
+            const size_t o = (size_t)(row_in ? i : 0) * W;
+            win[0] = row_in && c0 > 0 ? at(o + (c0 - 1)) : 0.0f;
+            win[1] = win[4], win[2] = win[5], win[3] = win[6];
+            win[8] = win[5], win[9] = win[6], win[10] = win[7];
+            win[11] = row_in && c0 + 4 < W ? at(o + (c0 + 4)) : 0.0f;
+        } else {
+            cols<GW, false>(win, i, c0 - d, H, W);
+            cols<GW, true>(win + GW, i, c0, H, W);
+            cols<GW, false>(win + 2 * GW, i, c0 + d, H, W);
+        }
+    }
+};
+
+// this thread's column group and chain segment: false when it has none
+struct DwItem { int c0, i0, iend; };
+template <int GW> __device__ __forceinline__ bool dw_item(const DwGeom &G, int blk, DwItem &it)
+{
+    const long long item = (long long)blk * DW_TPB + threadIdx.x;
+    if (item >= G.items) return false;
+    const int g = (int)(item % G.ngroups);
+    const long long t = item / G.ngroups;
+    const int r = (int)(t % G.nres);
+    const long long k0 = (t / G.nres) * DW_L;
+    const long long i0 = r + k0 * G.d, iend = i0 + (long long)DW_L * G.d;
+    it.c0 = g * GW;
+    it.i0 = (int)(i0 < G.H ? i0 : G.H);
+    it.iend = (int)(iend < G.H ? iend : G.H);
+    return true;
+}
+
+// MODE DW_FWD: a = x, out = y.  MODE DW_BWD: a = g, yv = y, out = g_x.
+template <int MODE, int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dw_apply(const float *__restrict__ a, const float *__restrict__ yv, const float *__restrict__ w,
+                                                     const float *__restrict__ scale, const float *__restrict__ shift, float *__restrict__ out, DwGeom G)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    DwItem it;
+    if (!dw_item<GW>(G, blk, it)) return;
+    const size_t po = (size_t)plane * G.H * G.W;
+    const float sc = scale[c];
+    DwSrc<MODE> src;
+    src.a = a + po, src.y = MODE == DW_BWD ? yv + po : nullptr, src.scale = sc;
+    float wk[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wk[k] = MODE == DW_FWD ? w[c * 9 + k] : w[c * 9 + 8 - k];
+    const float sh = MODE == DW_FWD ? shift[c] : 0.0f;
+    const int d = D1 ? 1 : G.d;
+    float win[3][3 * GW];
+    src.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
+    src.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
+    float *op = out + po;
+    for (int i = it.i0; i < it.iend; i += d) {
+        src.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
+        float res[GW];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            float acc = wk[0] * win[0][e];
+#pragma unroll
+            for (int k = 1; k < 9; ++k) acc = __builtin_fmaf(wk[k], win[k / 3][(k % 3) * GW + e], acc);
+            if constexpr (MODE == DW_FWD) {
+                float pre = acc * sc;
+                pre = pre + sh;
+                acc = pre <= 0.0f ? 0.0f : pre;          // a NaN stays a NaN, as torch's ReLU leaves it
+            }
+            res[e] = acc;
+        }
+        if constexpr (GW == 4) {
+            dw_f4 v;
+            v.x = res[0], v.y = res[1], v.z = res[2], v.w = res[3];
+            *reinterpret_cast<dw_f4 *>(op + (size_t)i * G.W + it.c0) = v;
+        } else {
+            op[(size_t)i * G.W + it.c0] = res[0];
+        }
+#pragma unroll
+        for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
+    }
+}
+
+// part[(plane * bpp + blk) * 9 + k] = this block's float64 sum of gp[p] x[p + k d]
+template <int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dw_wpart(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ x,
+                                                     const float *__restrict__ scale, double *__restrict__ part, DwGeom G)
+{
+    __shared__ double s[DW_TPB / 64][9];
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const size_t po = (size_t)plane * G.H * G.W;
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    DwItem it;
+    if (dw_item<GW>(G, blk, it)) {
+        DwSrc<DW_FWD> sx;
+        sx.a = x + po, sx.y = nullptr, sx.scale = 0.0f;
+        DwSrc<DW_BWD> sg;
+        sg.a = g + po, sg.y = yv + po, sg.scale = scale[c];
+        const int d = D1 ? 1 : G.d;
+        float win[3][3 * GW];
+        sx.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
+        sx.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
+        for (int i = it.i0; i < it.iend; i += d) {
+            sx.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
+            float gp[GW];
+            sg.template cols<GW, true>(gp, i, it.c0, G.H, G.W);
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                const double ge = (double)gp[e];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) acc[k] = __builtin_fma(ge, (double)win[k / 3][(k % 3) * GW + e], acc[k]);
+            }
+#pragma unroll
+            for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) s[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+        double t = s[0][threadIdx.x];
+        for (int q = 1; q < DW_TPB / 64; ++q) t += s[q][threadIdx.x];
+        part[(size_t)blockIdx.x * 9 + threadIdx.x] = t;
+    }
+}
+
+// g_w[c, k] = sum over images b, then blocks, in ascending order
+__global__ void __launch_bounds__(DW_TPB) k_dw_wsum(const double *__restrict__ part, float *__restrict__ gw, int B, int C, int bpp)
+{
+    const int e = blockIdx.x * DW_TPB + threadIdx.x;
+    if (e >= C * 9) return;
+    const int c = e / 9, k = e - c * 9;
+    double t = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double *row = part + ((size_t)b * C + c) * bpp * 9 + k;
+        for (int q = 0; q < bpp; ++q) t += row[(size_t)q * 9];
+    }
+    gw[e] = (float)t;
+}
+
+static int dw_check(const char *who, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d)
+{
+    if (B < 1 || C < 1 || H < 1 || W < 1 || d < 1) return fail(HALO_E_ARG, "%s: empty shape or dilation < 1", who);
+    if (H > DW_MAX_DIM || W > DW_MAX_DIM || d > DW_MAX_DIM || H * W > 0x7fffffffLL || B * C > ((int64_t)1 << 40) || C > 0x7fffffffLL / 9 ||
+        B > 0x7fffffffLL)
+        return fail(HALO_E_UNSUPPORTED, "%s: %lld x %lld planes of %lld x %lld, dilation %lld", who, (long long)B, (long long)C, (long long)H,
+                    (long long)W, (long long)d);
+    return HALO_OK;
+}
+
+static bool dw_vec(int64_t W, const void *p0, const void *p1, const void *p2, const void *p3)
+{
+    return W % 4 == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3) % 16) == 0;
+}
+
+static int dw_grid(const char *who, int64_t planes, const DwGeom &G, unsigned &grid)
+{
+    const int64_t n = planes * G.bpp;
+    if (n > 0x7fffffffLL) return fail(HALO_E_UNSUPPORTED, "%s: %lld blocks", who, (long long)n);
+    grid = (unsigned)n;
+    return HALO_OK;
+}
+
+template <int MODE>
+static void dw_launch_apply(bool vec, unsigned grid, hipStream_t st, const float *a, const float *yv, const float *w, const float *scale,
+                            const float *shift, float *out, const DwGeom &G)
+{
+    const dim3 g(grid), b(DW_TPB);
+    if (vec && G.d == 1) hipLaunchKernelGGL((k_dw_apply<MODE, 4, true>), g, b, 0, st, a, yv, w, scale, shift, out, G);
+    else if (vec) hipLaunchKernelGGL((k_dw_apply<MODE, 4, false>), g, b, 0, st, a, yv, w, scale, shift, out, G);
+    else hipLaunchKernelGGL((k_dw_apply<MODE, 1, false>), g, b, 0, st, a, yv, w, scale, shift, out, G);
+}
+
+}  // namespace halo
+
+using namespace halo;
+
+extern "C" size_t halo_dwconv_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t d)
+{
+    if (dw_check("halo_dwconv_workspace_bytes", B, C, H, W, d) != HALO_OK) return 0;
+    const int b1 = dw_geom(C, H, W, d, 1).bpp, b4 = W % 4 == 0 ? dw_geom(C, H, W, d, 4).bpp : 0;
+    return (size_t)(B * C) * (size_t)(b1 > b4 ? b1 : b4) * 9 * sizeof(double);
+}
+
+extern "C" int halo_dwconv3x3_affine_relu_fwd(const float *x, const float *w, const float *scale, const float *shift, float *y, int64_t B,
+                                              int64_t C, int64_t H, int64_t W, int64_t d, void *stream)
+{
+    const char *who = "halo_dwconv3x3_affine_relu_fwd";
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    if (!x || !w || !scale || !shift || !y) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = dw_vec(W, x, y, nullptr, nullptr);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    dw_launch_apply<DW_FWD>(vec, grid, (hipStream_t)stream, x, nullptr, w, scale, shift, y, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_dwconv3x3_affine_relu_bwd_data(const float *g, const float *y, const float *w, const float *scale, float *g_x, int64_t B,
+                                                   int64_t C, int64_t H, int64_t W, int64_t d, void *stream)
+{
+    const char *who = "halo_dwconv3x3_affine_relu_bwd_data";
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    if (!g || !y || !w || !scale || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = dw_vec(W, g, y, g_x, nullptr);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    dw_launch_apply<DW_BWD>(vec, grid, (hipStream_t)stream, g, y, w, scale, nullptr, g_x, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const float *x, const float *scale, float *g_w, int64_t B,
+                                                     int64_t C, int64_t H, int64_t W, int64_t d, void *workspace, size_t workspace_bytes,
+                                                     void *stream)
+{
+    const char *who = "halo_dwconv3x3_affine_relu_bwd_weight";
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    if (!g || !y || !x || !scale || !g_w) return fail(HALO_E_ARG, "%s: null argument", who);
+    const size_t need = halo_dwconv_workspace_bytes(B, C, H, W, d);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 8) != 0)
+        return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (8-byte aligned)", who, workspace_bytes, need);
+    const bool vec = dw_vec(W, g, y, x, nullptr);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    const dim3 gr(grid), bl(DW_TPB);
+    if (vec && d == 1) hipLaunchKernelGGL((k_dw_wpart<4, true>), gr, bl, 0, st, g, y, x, scale, part, G);
+    else if (vec) hipLaunchKernelGGL((k_dw_wpart<4, false>), gr, bl, 0, st, g, y, x, scale, part, G);
+    else hipLaunchKernelGGL((k_dw_wpart<1, false>), gr, bl, 0, st, g, y, x, scale, part, G);
+    hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
+    return check_launch(who);
+}

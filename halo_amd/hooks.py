@@ -339,3 +339,54 @@ def use_device_resize(cls):
                         "bind one first with halo_amd.install() or use_fused_feature_reweighting" % (cls.__name__, ", ".join(_PROTOCOLS)))
     cls._halo_device_resize = True
     return cls
+
+
+# ---------------------------------------------------------------- depthwise conv + frozen norm + ReLU of the separable blocks
+# The five DepthwiseSeparableConv2d blocks of the v3+ heads (core/models/classifier.py:40-85: parallel_branches[1..3], decoder[0],
+# decoder[1]) start with a depthwise 3x3 conv, a FrozenBatchNorm2d and a ReLU: four bandwidth-bound passes over tensors of 200 MB.
+# `use_fused_depthwise(block_cls)` binds `fused_dwsep_forward`: halo_amd.dwconv.depthwise_bn_relu (halo_dwconv.hip, which keeps the
+# stock statements outside its envelope) and then the three pointwise modules unchanged.  The hook sits on the BLOCK class, so it
+# composes with install(), use_fused_feature_reweighting and use_device_resize in any order and serves the non-hyper
+# DepthwiseSeparableASPP as well.  The previous forward is kept as `_unfused_forward`.  install() does not bind it.
+
+_DWSEP_ATTRS = ("depthwise_conv", "depthwise_bn", "depthwise_activate", "pointwise_conv", "pointwise_bn", "pointwise_activate")
+
+
+def fused_dwsep_forward(self, x):
+    from .dwconv import depthwise_bn_relu, torch_statement
+    if type(self.depthwise_activate) is torch.nn.ReLU:
+        x = depthwise_bn_relu(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate)
+    else:
+        x = torch_statement(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate)
+    x = self.pointwise_conv(x)
+    x = self.pointwise_bn(x)
+    x = self.pointwise_activate(x)
+    return x
+
+
+def _is_dwsep_class(cls):
+    """the reference's DepthwiseSeparableConv2d (by name), or an nn.Module class whose instances carry the six attributes: they are
+    class attributes, or the __init__ methods of the class assign them (read off the code objects: nothing is constructed)"""
+    if not isinstance(cls, type) or not issubclass(cls, torch.nn.Module):
+        return False
+    if any(k.__name__ == "DepthwiseSeparableConv2d" for k in cls.__mro__):
+        return True
+    names = set()
+    for klass in cls.__mro__:
+        init = klass.__dict__.get("__init__")
+        names.update(getattr(getattr(init, "__code__", None), "co_names", ()))
+    return all(hasattr(cls, a) or a in names for a in _DWSEP_ATTRS)
+
+
+def use_fused_depthwise(block_cls):
+    """Bind fused_dwsep_forward on a depthwise-separable block class (the reference's DepthwiseSeparableConv2d, or any nn.Module
+    class whose instances carry depthwise_conv, depthwise_bn, depthwise_activate, pointwise_conv, pointwise_bn,
+    pointwise_activate).  Returns the class; the forward it replaced is kept as `_unfused_forward`.  Idempotent."""
+    if not _is_dwsep_class(block_cls):
+        raise TypeError("use_fused_depthwise: %r is not a depthwise-separable block class (instances with %s)"
+                        % (block_cls, ", ".join(_DWSEP_ATTRS)))
+    if block_cls.__dict__.get("forward") is fused_dwsep_forward:
+        return block_cls
+    block_cls._unfused_forward = _inherited(block_cls, "forward")
+    block_cls.forward = fused_dwsep_forward
+    return block_cls

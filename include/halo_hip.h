@@ -403,6 +403,24 @@ int halo_hfr_bwd_apply(const float *x, int64_t B, int64_t C, int64_t P, const fl
                        const float *g, const double *gsums, float *g_x, float *g_W1, float *g_b1, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* ---- depthwise 3x3 conv + frozen norm + ReLU: the first half of DepthwiseSeparableConv2d (core/models/classifier.py:78-81) ----
+ *  x, y, g, g_x (B, C, H, W) f32 dense NCHW; w (C, 1, 3, 3) f32; scale, shift (C) f32; dilation d >= 1 = padding, stride 1, zeros.
+ *    pre = (sum_{ky,kx} w[c,ky,kx] x[b,c,i+(ky-1)d,j+(kx-1)d]) * scale[c] + shift[c]   (two roundings), y = max(pre, 0)
+ *    gp = g [y > 0] scale[c];  g_x[p] = sum_k w[c,k] gp[p - k d];  g_w[c,k] = sum_{b,p} gp[b,c,p] x[b,c,p + k d]
+ *  The 9-term sums run over the input positions in ascending (row, column) order, the first product rounded and every further
+ *  term one fma, whatever the route; g_w is summed in float64 (per-block rows in the workspace, added in ascending (image,
+ *  block) order) and rounded once.  No atomics: repeated calls give identical bits.  Only bwd_weight needs the workspace
+ *  (8-byte aligned).  HALO_E_UNSUPPORTED: H, W or d above 2^24, H * W above 2^31 - 1; HALO_E_ARG: an empty shape, d < 1 or a
+ *  missing pointer; HALO_E_WORKSPACE: a short workspace. */
+size_t halo_dwconv_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t d);
+int halo_dwconv3x3_affine_relu_fwd(const float *x, const float *w, const float *scale, const float *shift, float *y, int64_t B, int64_t C,
+                                   int64_t H, int64_t W, int64_t d, void *stream);
+int halo_dwconv3x3_affine_relu_bwd_data(const float *g, const float *y, const float *w, const float *scale, float *g_x, int64_t B,
+                                        int64_t C, int64_t H, int64_t W, int64_t d, void *stream);
+int halo_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const float *x, const float *scale, float *g_w, int64_t B,
+                                          int64_t C, int64_t H, int64_t W, int64_t d, void *workspace, size_t workspace_bytes,
+                                          void *stream);
+
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
 int halo_event_record(void *event, void *stream);
