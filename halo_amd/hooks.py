@@ -390,3 +390,129 @@ def use_fused_depthwise(block_cls):
     block_cls._unfused_forward = _inherited(block_cls, "forward")
     block_cls.forward = fused_dwsep_forward
     return block_cls
+
+
+# ---------------------------------------------------------------- frozen norm + residual add + ReLU of the backbone and the heads
+# With MODEL.FREEZE_BN every norm of the ResNet backbone and every dense norm of the heads is a FrozenBatchNorm2d whose forward is
+# torch statements (core/models/layers.py): a broadcast mul and a broadcast add over the activation, then an in-place ReLU, and at
+# the end of a residual block an in-place `out += identity` and another ReLU.  halo_amd.norm.norm_relu (halo_norm.hip) runs each
+# such chain as one pass with the chain's own roundings, so a hooked model returns the unhooked model's bits.  Two opt-in hooks,
+# neither bound by install():
+#   use_fused_frozen_norm(block_cls)   class level: the two residual blocks of core/models/resnet.py (Bottleneck, BasicBlock);
+#   fuse_norm_relu_pairs(module)       instance level: (FrozenBatchNorm2d, nn.ReLU) neighbours that a container calls in sequence --
+#                                      the stem inside the feature extractor's IntermediateLayerGetter, the v3+ heads'
+#                                      parallel_branches[0], global_branch, bottleneck and shortcut.
+# The separable blocks' pointwise_bn + pointwise_activate stay as they are: fusing them needs a forward that composes with
+# use_fused_depthwise, whose results are not bit-equal to the stock depthwise conv, so nothing here switches that on.
+
+_RESIDUAL_ATTRS = ("conv1", "bn1", "conv2", "bn2", "relu", "downsample")
+
+
+def fused_residual_forward(self, x):
+    from .norm import norm_relu
+    if type(self.relu) is not torch.nn.ReLU:
+        return self._unfused_forward(x)
+    out = norm_relu(self.conv1(x), self.bn1)
+    if getattr(self, "conv3", None) is not None:             # the Bottleneck form
+        out = norm_relu(self.conv2(out), self.bn2)
+        out, last = self.conv3(out), self.bn3
+    else:                                                    # the BasicBlock form
+        out, last = self.conv2(out), self.bn2
+    down = self.downsample
+    if down is None:
+        return norm_relu(out, last, residual=x)
+    if type(down) is torch.nn.Sequential and len(down) == 2 and isinstance(down[0], torch.nn.Conv2d):
+        return norm_relu(out, last, residual=down[0](x), residual_bn=down[1])      # the downsample norm is folded into the pass
+    return norm_relu(out, last, residual=down(x))
+
+
+def _is_residual_class(cls):
+    """the reference's Bottleneck / BasicBlock (by name), or an nn.Module class whose instances carry conv1, bn1, conv2, bn2, relu
+    and downsample (class attributes, or names its __init__ methods assign: nothing is constructed)"""
+    if not isinstance(cls, type) or not issubclass(cls, torch.nn.Module):
+        return False
+    if any(k.__name__ in ("Bottleneck", "BasicBlock") for k in cls.__mro__):
+        return True
+    names = set()
+    for klass in cls.__mro__:
+        init = klass.__dict__.get("__init__")
+        names.update(getattr(getattr(init, "__code__", None), "co_names", ()))
+    return all(hasattr(cls, a) or a in names for a in _RESIDUAL_ATTRS)
+
+
+def use_fused_frozen_norm(block_cls):
+    """Bind fused_residual_forward on a residual block class of the Bottleneck form (conv1, bn1, conv2, bn2, conv3, bn3, relu,
+    downsample) or the BasicBlock form (the same without conv3 / bn3).  Returns the class; the forward it replaced is kept as
+    `_unfused_forward` and serves a block whose `relu` is not nn.ReLU.  Idempotent."""
+    if not _is_residual_class(block_cls):
+        raise TypeError("use_fused_frozen_norm: %r is not a residual block class (instances with %s)" % (block_cls, ", ".join(_RESIDUAL_ATTRS)))
+    if block_cls.__dict__.get("forward") is fused_residual_forward:
+        return block_cls
+    block_cls._unfused_forward = _inherited(block_cls, "forward")
+    block_cls.forward = fused_residual_forward
+    return block_cls
+
+
+class _PairNorm:
+    """the call of a norm whose next sibling is a ReLU: relu(norm(x)) in one pass"""
+
+    def __init__(self, norm):
+        self.norm = norm
+
+    def __call__(self, x):
+        from .norm import fallback_reason, fused_norm_relu
+        norm = self.norm
+        if fallback_reason(x, norm) is not None:
+            return F.relu(type(norm).forward(norm, x), inplace=True)
+        return fused_norm_relu(x, norm)
+
+
+class _PairRelu:
+    """the call of the ReLU behind such a norm: its input is already rectified"""
+
+    def __call__(self, x):
+        return x
+
+
+def _pair_containers(module):
+    for m in module.modules():
+        if isinstance(m, torch.nn.Sequential) or (isinstance(m, torch.nn.ModuleDict) and type(m).__name__ == "IntermediateLayerGetter"):
+            yield m
+
+
+def fuse_norm_relu_pairs(module):
+    """In every nn.Sequential and every IntermediateLayerGetter (an nn.ModuleDict subclass of that name) under `module`, make each
+    FrozenBatchNorm2d child whose next sibling is an nn.ReLU return halo_amd.norm.norm_relu(x, norm) and that ReLU return its
+    input.  Both get an instance-level `forward`; no module is added, removed or renamed, so state_dict(), named_modules() and a
+    checkpoint loaded afterwards are unaffected.  A norm or a ReLU object that `module` holds in more than one place, and a norm
+    whose output the container returns (IntermediateLayerGetter.return_layers), is left alone.  Returns the number of pairs
+    fused (0 on a second call); unfuse_norm_relu_pairs(module) undoes it."""
+    from .dwconv import _is_frozen
+    uses = {}
+    for m in module.modules():
+        for child in m._modules.values():
+            if child is not None:
+                uses[id(child)] = uses.get(id(child), 0) + 1
+    fused = 0
+    for box in _pair_containers(module):
+        kept = getattr(box, "return_layers", None) or {}
+        items = [(n, c) for n, c in box._modules.items() if c is not None]
+        for (name, norm), (_, act) in zip(items, items[1:]):
+            if not _is_frozen(norm) or type(act) is not torch.nn.ReLU or name in kept:
+                continue
+            if uses[id(norm)] != 1 or uses[id(act)] != 1 or "forward" in norm.__dict__ or "forward" in act.__dict__:
+                continue
+            norm.forward, act.forward = _PairNorm(norm), _PairRelu()
+            fused += 1
+    return fused
+
+
+def unfuse_norm_relu_pairs(module):
+    """Undo fuse_norm_relu_pairs(module).  Returns the number of pairs restored."""
+    n = 0
+    for m in module.modules():
+        f = m.__dict__.get("forward")
+        if isinstance(f, (_PairNorm, _PairRelu)):
+            del m.__dict__["forward"]
+            n += isinstance(f, _PairNorm)
+    return n

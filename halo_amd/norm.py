@@ -1,0 +1,186 @@
+"""A frozen norm, the residual add and the ReLU of a ResNet block (core/models/resnet.py:53-69, 92-112) on the device.
+
+Every shipped config trains deeplabv3plus_resnet101 with MODEL.FREEZE_BN, so every norm of the backbone and every dense norm of
+the heads is a FrozenBatchNorm2d (core/models/layers.py) whose forward is torch statements: four tiny kernels for scale and bias,
+a broadcast mul and a broadcast add over the activation, then an in-place ReLU -- and, at the end of a residual block, an in-place
+`out += identity` and another ReLU.  `norm_relu(x, bn, residual=None, residual_bn=None)` computes
+
+    out = bn(x);   out += residual_bn(residual)  or  out += residual;   relu(out)
+
+and the gradients for x and residual with halo_norm.hip: one read of every operand and one write, forward and backward; the
+backward keeps y, scale and r_scale and nothing else.  The kernel runs the chain's own operations with the chain's roundings
+(product, sum, sum, comparison; no fma), so its results are the chain's bits, not an approximation of them.
+
+Served (fallback_reason is None): x float32 (B, C, H, W) on the device, contiguous NCHW, non-empty, no autocast; bn (and
+residual_bn) a module whose type is named FrozenBatchNorm2d with its four float32 buffers of C channels on x's device; residual
+of x's shape, dtype and device, contiguous.  Anything else -- eval-mode nn.BatchNorm2d (one ATen kernel with another rounding
+order), channels-last, other dtypes, CPU tensors -- runs the stock statements (torch_statement), which keep torch's results and
+errors.  One rule is about speed alone: a small tensor that needs a gradient runs the stock statements too (AUTOGRAD_MIN_ELEMENTS).
+
+scale and shift are the module's own two statements as torch ops (halo_amd.dwconv.scale_shift: no eps).  The stock module
+recomputes them on every call; here the pair is cached per norm instance, keyed on the identity and the `_version` of the four
+buffers, which the entry holds references to.  load_state_dict and every in-place write through the buffer bump `_version`;
+.to() / .cuda() / an assignment replace the tensor object: each makes the next call recompute.  The one write torch does not
+version is one through a detached alias (`bn.weight.data.mul_()`, or a write through a tensor obtained with .detach() under
+inference mode); call `forget(bn)` after such a write.  A buffer without a version counter (an inference-mode tensor) is never
+cached.
+"""
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .dwconv import _is_frozen, scale_shift
+from .hfr import _autocast
+
+_BUFFERS = ("weight", "bias", "running_mean", "running_var")
+_cache = weakref.WeakKeyDictionary()          # norm module -> (the four keyed buffers, their versions, (scale, shift))
+launches = {"fwd": 0, "bwd": 0}               # device launches issued by this module (tests count them)
+# A speed rule, not a correctness rule (both sides return the same bits).  When a gradient will be asked for, a forward + backward
+# pair through the Python autograd node costs about 0.16 ms of host time whatever the size; measured alone, back to back, the stock
+# chain's pair is shorter than that below these element counts (2 x 512 x 80 x 160 loses without a residual_bn
+# and wins with one, 2 x 1024 x 80 x 160 wins in every variant).  Smaller tensors that require a gradient run the stock statements;
+# without a gradient (no_grad, inputs that need none) every size is served.  Set both to 0 to serve every size.
+AUTOGRAD_MIN_ELEMENTS = {"plain": 2 * 1024 * 80 * 160, "affine": 2 * 512 * 80 * 160}
+
+
+def torch_statement(x, bn, residual=None, residual_bn=None):
+    """the stock statements of a block's tail (resnet.py:103-110), or of `bn, relu` alone"""
+    out = bn(x)
+    if residual is not None:
+        out += residual if residual_bn is None else residual_bn(residual)
+    return F.relu(out, inplace=True)
+
+
+def _norm_reason(bn, C, device, what):
+    if not _is_frozen(bn):
+        return "%s is not a FrozenBatchNorm2d" % what
+    for n in _BUFFERS:
+        t = bn._buffers[n]
+        if t.dtype != torch.float32 or t.device != device:
+            return "%s.%s is not float32 on %s" % (what, n, device)
+        if t.dim() != 1 or t.numel() != C:
+            return "%s.%s has shape %s, x has %d channels" % (what, n, tuple(t.shape), C)
+    return None
+
+
+def fallback_reason(x, bn, residual=None, residual_bn=None):
+    """why norm_relu(x, bn, residual, residual_bn) runs the torch statements (None: the fused path serves it).  Reads no device
+    memory."""
+    reason = _envelope_reason(x, bn, residual, residual_bn)
+    if reason is None and torch.is_grad_enabled() and (getattr(x, "requires_grad", False) or getattr(residual, "requires_grad", False)):
+        least = AUTOGRAD_MIN_ELEMENTS["affine" if residual_bn is not None else "plain"]
+        if x.numel() < least:
+            return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (x.numel(), least)
+    return reason
+
+
+def _envelope_reason(x, bn, residual, residual_bn):
+    if not torch.is_tensor(x) or x.dim() != 4:
+        return "x is not a (B, C, H, W) tensor"
+    if x.dtype != torch.float32:
+        return "x is %s, not float32" % x.dtype
+    if _autocast():
+        return "autocast is enabled"
+    if not x.is_cuda:
+        return "x is not on a ROCm device"
+    if x.numel() == 0:
+        return "empty input"
+    if not x.is_contiguous():
+        return "x is not contiguous NCHW"
+    C = x.shape[1]
+    if x.shape[2] * x.shape[3] > 2 ** 31 - 1025:
+        return "plane of %d x %d" % (x.shape[2], x.shape[3])
+    r = _norm_reason(bn, C, x.device, "bn")
+    if r is not None:
+        return r
+    if residual is None:
+        if residual_bn is not None:
+            return "residual_bn without a residual"
+        return None
+    if not torch.is_tensor(residual) or residual.shape != x.shape:
+        return "residual does not have x's shape"
+    if residual.dtype != x.dtype or residual.device != x.device:
+        return "residual is not %s on %s" % (x.dtype, x.device)
+    if not residual.is_contiguous():
+        return "residual is not contiguous NCHW"
+    if residual_bn is not None:
+        return _norm_reason(residual_bn, C, x.device, "residual_bn")
+    return None
+
+
+def cached_scale_shift(bn):
+    """(scale, shift) of a frozen norm; the tensors of the previous call while its four buffers are the same objects at the same
+    versions"""
+    bufs = tuple(bn._buffers[n] for n in _BUFFERS)
+    try:
+        versions = tuple(t._version for t in bufs)
+    except RuntimeError:                       # inference tensors carry no version counter: nothing to key on
+        _cache.pop(bn, None)
+        return scale_shift(bn)
+    hit = _cache.get(bn)
+    if hit is not None and hit[1] == versions and all(a is b for a, b in zip(hit[0], bufs)):
+        return hit[2]
+    pair = scale_shift(bn)
+    _cache[bn] = (bufs, versions, pair)
+    return pair
+
+
+def forget(bn=None):
+    """drop the cached (scale, shift) of one norm, or of all"""
+    if bn is None:
+        _cache.clear()
+    else:
+        _cache.pop(bn, None)
+
+
+class _NormReluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, r, r_scale, r_shift):
+        B, C, H, W = x.shape
+        y = torch.empty_like(x)
+        launches["fwd"] += 1
+        _lib.check(_lib.lib().halo_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(r), _lib.ptr(r_scale),
+                                                   _lib.ptr(r_shift), _lib.ptr(y), B, C, H * W, _lib.stream_ptr(x.device)),
+                   "halo_affine_relu_fwd")
+        ctx.save_for_backward(y, scale, r_scale)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, scale, r_scale = ctx.saved_tensors
+        B, C, H, W = y.shape
+        want_x, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        gx = gr = None
+        if want_x or want_r:
+            g = g.to(device=y.device, dtype=torch.float32).contiguous()
+            gx = torch.empty_like(y) if want_x else None
+            gr = torch.empty_like(y) if want_r else None
+            launches["bwd"] += 1
+            _lib.check(_lib.lib().halo_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(r_scale), _lib.ptr(gx),
+                                                       _lib.ptr(gr), B, C, H * W, _lib.stream_ptr(y.device)), "halo_affine_relu_bwd")
+        return gx, None, None, gr, None, None
+
+
+def norm_relu(x, bn, residual=None, residual_bn=None):
+    """relu(bn(x)), relu(bn(x) + residual) or relu(bn(x) + residual_bn(residual)) of frozen norms, x (B, C, H, W): the stock
+    chain's bits.  Differentiable w.r.t. x and residual; x is not modified.  Outside the served envelope (fallback_reason) it
+    returns torch_statement(x, bn, residual, residual_bn)."""
+    if fallback_reason(x, bn, residual, residual_bn) is not None:
+        return torch_statement(x, bn, residual, residual_bn)
+    return fused_norm_relu(x, bn, residual, residual_bn)
+
+
+def fused_norm_relu(x, bn, residual=None, residual_bn=None):
+    """norm_relu for arguments that fallback_reason has accepted"""
+    scale, shift = cached_scale_shift(bn)
+    r_scale = r_shift = None
+    if residual_bn is not None:
+        r_scale, r_shift = cached_scale_shift(residual_bn)
+    return _NormReluFn.apply(x, scale, shift, residual, r_scale, r_shift)
+
+
+__all__ = ["norm_relu", "torch_statement", "fallback_reason", "cached_scale_shift", "forget"]

@@ -421,6 +421,22 @@ int halo_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const 
                                           int64_t C, int64_t H, int64_t W, int64_t d, void *workspace, size_t workspace_bytes,
                                           void *stream);
 
+/* ---- frozen norm + residual add + ReLU of a ResNet block (core/models/resnet.py:53-69, 92-112; core/models/layers.py) ----
+ *  x, r, y, g, g_x, g_r (B, C, HW) f32 dense NCHW planes; scale, shift, r_scale, r_shift (C) f32.
+ *    pre = fl(fl(x scale[c]) + shift[c]);  id = r  or  fl(fl(r r_scale[c]) + r_shift[c]);  y = relu(pre)  or  relu(fl(pre + id))
+ *    gp = y <= 0 ? 0 : g;  g_x = fl(gp scale[c]);  g_r = gp  or  fl(gp r_scale[c])
+ *  relu(s) = s <= 0 ? 0 : s keeps a NaN; a NaN y lets g through.  Every product and sum is rounded on its own (no fma): the bits
+ *  are those of the torch statements `x * scale + bias; out += identity; relu_(out)` and of their autograd backward.
+ *  fwd: r == NULL: no residual; r_scale == NULL: r is added as it stands; r_scale and r_shift come together.  bwd: a NULL g_x or
+ *  g_r is neither computed nor written; r_scale == NULL: g_r = gp.  y must not overlap x or r; g_x and g_r must not overlap g, y.
+ *  HW % 4 == 0 with every operand 16-byte aligned runs 16-byte accesses, anything else one element per lane: same statements,
+ *  same bits.  HALO_E_ARG: an empty shape, a missing pointer, r_scale without r_shift or without r, bwd with neither output;
+ *  HALO_E_UNSUPPORTED: HW above 2^31 - 1025 or more than 2^31 - 1 workgroups. */
+int halo_affine_relu_fwd(const float *x, const float *scale, const float *shift, const float *r, const float *r_scale, const float *r_shift,
+                         float *y, int64_t B, int64_t C, int64_t HW, void *stream);
+int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *r_scale, float *g_x, float *g_r, int64_t B,
+                         int64_t C, int64_t HW, void *stream);
+
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
 int halo_event_record(void *event, void *stream);
