@@ -50,6 +50,11 @@ def host_is_stale():
     return any(os.path.getmtime(p) > t for p in [os.path.join(CSRC, f) for f in HOST_SOURCES] + [os.path.join(HERE, "..", "include", "halo_host.h")])
 
 
+def host_cc():
+    """the C compiler of the host-side pieces: $CC, else gcc / cc, else hipcc's clang"""
+    return os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc") or _hipcc()
+
+
 def build_host(force=False):
     """libhalo_host.so: the CPU-side helpers (no HIP), compiled with the system C compiler."""
     if not force and not host_is_stale():
@@ -61,7 +66,7 @@ def build_host(force=False):
         try:
             if not force and not host_is_stale():
                 return HOST_SO
-            cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc") or _hipcc()
+            cc = host_cc()
             tmp = HOST_SO + ".tmp.%d" % os.getpid()
             cmd = [cc, "-O3", "-std=c11", "-fPIC", "-shared", "-pthread", "-Wall"] + [os.path.join(CSRC, f) for f in HOST_SOURCES] + ["-o", tmp]
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -23,10 +23,28 @@ FLAG_NORMALIZE = 1
 
 
 def score_flags(normalize, padding_mode="zeros"):
-    """the flags word of the halo_score_maps* calls: bit 0 normalise, bits 8-9 the padding mode"""
+    """halo_score_args.flags: bit 0 normalise, bits 8-9 the padding mode"""
     return (FLAG_NORMALIZE if normalize else 0) | (PAD[padding_mode] << 8)
 
 _i64, _dbl, _int, _vp, _sz = C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_size_t
+
+SCORE_FULL, SCORE_LR, SCORE_LR_GRAM = 0, 1, 2                       # HALO_SCORE_*: halo_score_args.route
+
+
+class ScoreArgs(C.Structure):
+    """halo_score_args of include/halo_hip.h, field for field (tests/test_abi.py compiles the header and compares the layouts)"""
+    _fields_ = [("struct_bytes", _sz), ("route", _int),
+                ("logit", _vp), ("logit_bstride", _i64), ("hl", _i64), ("wl", _i64),
+                ("feat", _vp), ("feat_dtype", _int), ("feat_bstride", _i64), ("hf", _i64), ("wf", _i64),
+                ("gt", _vp), ("active", _vp),
+                ("B", _i64), ("O", _i64), ("C", _i64), ("H", _i64), ("W", _i64),
+                ("unc_type", _int), ("pur_type", _int), ("flags", _int), ("ksize", _int), ("pksize", _int), ("K", _i64), ("c", _dbl),
+                ("score", _vp), ("impurity", _vp), ("uncertainty", _vp),
+                ("workspace", _vp), ("workspace_bytes", _sz),
+                ("tail_stream", _vp), ("score_range", _vp),
+                ("ev_logit_start", _vp), ("ev_logit_stop", _vp), ("ev_feat_start", _vp), ("ev_feat_mid", _vp), ("ev_feat_stop", _vp),
+                ("ev_tail_stop", _vp)]
+
 
 # name -> (restype, argtypes); must list every symbol include/halo_hip.h declares
 SIGNATURES = {
@@ -47,20 +65,8 @@ SIGNATURES = {
     "halo_bilinear_upsample": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp]),
     "halo_bilinear_upsample_bwd": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp]),
     "halo_score_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "halo_score_maps": (_int, [_vp, _i64, _vp, _int, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int,
-                               _int, _int, _int, _i64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "halo_score_maps_timed": (_int, [_vp, _i64, _vp, _int, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int,
-                                     _int, _int, _int, _i64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "halo_score_maps_split": (_int, [_vp, _i64, _vp, _int, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int,
-                                     _int, _int, _int, _i64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "halo_score_lr_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
-    "halo_score_maps_lr": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                  _int, _int, _int, _int, _int, _i64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "halo_score_lr_gram_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
-    "halo_score_maps_lr_gram": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                       _int, _int, _int, _int, _int, _i64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "halo_score_maps_lr_timed": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                        _int, _int, _int, _int, _int, _i64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "halo_score_args_workspace_bytes": (_sz, [C.POINTER(ScoreArgs)]),
+    "halo_score": (_int, [C.POINTER(ScoreArgs), _vp]),
     "halo_region_uncertainty": (_int, [_vp, _i64, _int, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _sz, _vp]),
     "halo_region_impurity": (_int, [_vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _int, _vp]),
     "halo_quantize_radius": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _vp, _vp, _sz, _vp]),
@@ -97,17 +103,13 @@ SIGNATURES = {
     "halo_select_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "halo_score_range_bytes": (_sz, [_i64]),
     "halo_score_range": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp]),
-    "halo_greedy_select_ranged": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _sz, _int, _vp, _vp]),
-    "halo_greedy_select_ex": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _vp, _sz, _int, _vp, _vp, _vp]),
     "halo_greedy_select": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _sz, _int, _vp]),
+                                  _vp, _sz, _int, _vp, _vp, _vp]),
 }
 
 # must equal HALO_ABI_VERSION of include/halo_hip.h; bumped whenever an exported signature changes, so a stale
 # library with the same symbol names but older argument lists is refused instead of being called with shifted arguments
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lock = threading.Lock()
 _handle = None
@@ -264,3 +266,8 @@ def stream_ptr(device=None):
 
 def ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def addr(t):
+    """a tensor's device address for a pointer field of a ctypes.Structure (None = NULL)"""
+    return None if t is None else t.data_ptr()

@@ -66,10 +66,10 @@ def greedy_select(score, n_regions, active_radius, mask_radius, active, selected
     ws = _workspace(dev, nws, "select")
     if score_range is not None:
         assert score_range.is_contiguous() and score_range.device == dev and score_range.numel() >= L.halo_score_range_bytes(B)
-    rc = L.halo_greedy_select_ex(_lib.ptr(score), _lib.dtype_code(score), B, H, W, n, int(active_radius),
-                                 int(mask_radius), _lib.ptr(active), _lib.ptr(selected), _lib.ptr(active_mask),
-                                 _lib.ptr(ground_truth), _lib.ptr(picks), _lib.ptr(n_picked), _lib.ptr(ws), ws.numel(),
-                                 method, _lib.ptr(score_range), _lib.ptr(handover), _lib.stream_ptr(dev))
+    rc = L.halo_greedy_select(_lib.ptr(score), _lib.dtype_code(score), B, H, W, n, int(active_radius),
+                              int(mask_radius), _lib.ptr(active), _lib.ptr(selected), _lib.ptr(active_mask),
+                              _lib.ptr(ground_truth), _lib.ptr(picks), _lib.ptr(n_picked), _lib.ptr(ws), ws.numel(),
+                              method, _lib.ptr(score_range), _lib.ptr(handover), _lib.stream_ptr(dev))
     _lib.check(rc, "halo_greedy_select")
     return (picks, n_picked) if return_picks else None
 

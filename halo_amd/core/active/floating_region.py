@@ -77,6 +77,50 @@ def new_score_range(B, dev):
     return torch.empty((int(B), int(n)), dtype=torch.uint8, device=dev)
 
 
+def _labels_and_mask(unc_type, pur_type, ground_truth, active, shape):
+    """(gt, act): the int64 labels where the chosen types read them (None otherwise) and the uint8 form of the optional mask"""
+    gt = None
+    if unc_type == "oracle_acc" or pur_type == "oracle_ripu":
+        if ground_truth is None:
+            raise ValueError("ground_truth is required for '%s'/'%s'" % (unc_type, pur_type))
+        gt = ground_truth.reshape(shape).to(torch.int64).contiguous()
+    act = None
+    if active is not None:
+        act = active.reshape(shape).contiguous()
+        act = act.view(torch.uint8) if act.dtype == torch.bool else act.to(torch.uint8)
+    return gt, act
+
+
+def _run_scorer(route, logit, feat, size, gt, act, outs, *, unc_type, pur_type, flags, ksize, psize, K, c,
+                events, score_range=None, tail_stream=None, workspace=None):
+    """The one call into the scorer (halo_score): fill a halo_score_args from prepared tensors -- dense, on one device, logit
+    (B,O,h,w) float32 and feat (B,C,h',w') float32 | float64 or None, at the maps' resolution `size` (route FULL) or below it --
+    size the scratch for the route, enqueue on the current stream.  outs = (score, impurity | None, uncertainty | None);
+    events = {halo_score_args field: handle from halo_event_create | None}."""
+    L = _lib.lib()
+    dev = logit.device
+    B, O, hl, wl = logit.shape
+    Cc, hf, wf = feat.shape[1:] if feat is not None else (0, 0, 0)
+    a = _lib.ScoreArgs(struct_bytes=_lib.C.sizeof(_lib.ScoreArgs), route=route,
+                       logit=logit.data_ptr(), logit_bstride=logit.stride(0), hl=hl, wl=wl,
+                       feat=_lib.addr(feat), feat_dtype=_lib.dtype_code(feat) if feat is not None else _lib.F64,
+                       feat_bstride=feat.stride(0) if feat is not None else 0, hf=hf, wf=wf,
+                       gt=_lib.addr(gt), active=_lib.addr(act), B=B, O=O, C=Cc, H=size[0], W=size[1],
+                       unc_type=_lib.UNC.get(unc_type, _lib.UNC_ZEROS), pur_type=_lib.PUR[pur_type], flags=flags,
+                       ksize=int(ksize), pksize=int(psize), K=int(K), c=float(c),
+                       score=_lib.addr(outs[0]), impurity=_lib.addr(outs[1]), uncertainty=_lib.addr(outs[2]),
+                       tail_stream=None if tail_stream is None else tail_stream.cuda_stream,
+                       score_range=_lib.addr(score_range), **events)
+    nws = L.halo_score_args_workspace_bytes(_lib.C.byref(a))
+    if workspace is not None:
+        assert workspace.dtype == torch.uint8 and workspace.numel() >= nws and workspace.device == dev
+    ws = workspace if workspace is not None else _workspace(dev, nws, "score")
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if score_range is not None:
+        assert score_range.is_contiguous() and score_range.device == dev and score_range.numel() >= L.halo_score_range_bytes(B)
+    _lib.check(L.halo_score(_lib.C.byref(a), _lib.stream_ptr(dev)), "halo_score")
+
+
 def score_maps(logit, decoder_out=None, unc_type=None, pur_type=None, normalize=False, ground_truth=None,
                size=3, purity_size=None, K=100, c=1.0, active=None, want_maps=True, out=None, events=None, score_range=None,
                tail_stream=None, workspace=None, maps=None, padding_mode="zeros"):
@@ -88,7 +132,7 @@ def score_maps(logit, decoder_out=None, unc_type=None, pur_type=None, normalize=
     buffers); events: optional (start, stop) handles from halo_event_create, recorded around the
     feature-reduction kernel; score_range: optional new_score_range(B, dev) to receive the maps' value ranges.
     tail_stream (pipelined callers): a torch stream that receives everything behind the passes over the inputs
-    (halo_score_maps_split; needs `events`, whose stop event is the fork, a `workspace` of its own per call in flight --
+    (halo_score_args.tail_stream; needs `events`, whose stop event is the fork, a `workspace` of its own per call in flight --
     score_workspace(B, H, W, dev) -- and preallocated `maps` = (impurity, uncertainty)); the results are complete on it.
     padding_mode: nn.Conv2d's padding_mode of the two box windows ('zeros' | 'reflect' | 'replicate' | 'circular').
     Returns (score, impurity, uncertainty), each (B,H,W); the last two are None if not want_maps.
@@ -106,28 +150,16 @@ def score_maps(logit, decoder_out=None, unc_type=None, pur_type=None, normalize=
         logit = logit.contiguous()
     need_feat = pur_type in ("hyper", "radius", "euc_norm")
     feat = None
-    Cc, fdt, fbs = 0, _lib.F64, 0
     if need_feat:
         if decoder_out is None:
             raise ValueError("decoder_out is required for purity type '%s'" % pur_type)
         feat = decoder_out
         if feat.dtype not in (torch.float32, torch.float64):
             feat = feat.float()
-        Cc = feat.shape[1]
         assert feat.shape[0] == B and feat.shape[2:] == (H, W), "decoder_out shape mismatch"
         if feat.stride()[1:] != (H * W, W, 1):
             feat = feat.contiguous()
-        fdt, fbs = _lib.dtype_code(feat), feat.stride(0)
-    need_gt = unc_type == "oracle_acc" or pur_type == "oracle_ripu"
-    gt = None
-    if need_gt:
-        if ground_truth is None:
-            raise ValueError("ground_truth is required for '%s'/'%s'" % (unc_type, pur_type))
-        gt = ground_truth.reshape(B, H, W).to(torch.int64).contiguous()
-    act = None
-    if active is not None:
-        act = active.reshape(B, H, W).contiguous()
-        act = act.view(torch.uint8) if act.dtype == torch.bool else act.to(torch.uint8)
+    gt, act = _labels_and_mask(unc_type, pur_type, ground_truth, active, (B, H, W))
     odt = score_dtype(pur_type, feat)
     if B == 0 or H == 0 or W == 0:                      # empty batch / empty image: nothing to launch
         e = torch.empty((B, H, W), dtype=odt, device=dev)
@@ -143,33 +175,14 @@ def score_maps(logit, decoder_out=None, unc_type=None, pur_type=None, normalize=
     else:
         imp = torch.empty((B, H, W), dtype=odt, device=dev) if want_maps else None
         unc = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_maps else None
-    L = _lib.lib()
-    nws = L.halo_score_workspace_bytes(B, H, W)
-    if workspace is not None:
-        assert workspace.dtype == torch.uint8 and workspace.numel() >= nws and workspace.device == dev
-        ws = workspace
-    else:
-        ws = _workspace(dev, nws, "score")
-    psize = size if purity_size is None else purity_size
-    ev0, ev1 = events if events is not None else (None, None)
-    if score_range is not None:
-        assert score_range.is_contiguous() and score_range.device == dev and score_range.numel() >= L.halo_score_range_bytes(B)
     if tail_stream is not None:
         assert events is not None and workspace is not None and (maps is not None or not want_maps), \
             "tail_stream needs events, a workspace of the call's own and preallocated maps"
-        rc = L.halo_score_maps_split(_lib.ptr(logit), logit.stride(0), _lib.ptr(feat), fdt, fbs, _lib.ptr(gt),
-                                     _lib.ptr(act), B, O, Cc, H, W, _lib.UNC.get(unc_type, _lib.UNC_ZEROS),
-                                     _lib.PUR[pur_type], _lib.score_flags(normalize, padding_mode), int(size), int(psize), int(K), float(c),
-                                     _lib.ptr(score), _lib.ptr(imp), _lib.ptr(unc), _lib.ptr(ws), ws.numel(),
-                                     _lib.stream_ptr(dev), _lib.C.c_void_p(tail_stream.cuda_stream), ev0, ev1, _lib.ptr(score_range))
-        _lib.check(rc, "halo_score_maps_split")
-        return score, imp, unc
-    rc = L.halo_score_maps_timed(_lib.ptr(logit), logit.stride(0), _lib.ptr(feat), fdt, fbs, _lib.ptr(gt),
-                                 _lib.ptr(act), B, O, Cc, H, W, _lib.UNC.get(unc_type, _lib.UNC_ZEROS),
-                                 _lib.PUR[pur_type], _lib.score_flags(normalize, padding_mode), int(size), int(psize), int(K), float(c),
-                                 _lib.ptr(score), _lib.ptr(imp), _lib.ptr(unc), _lib.ptr(ws), ws.numel(),
-                                 _lib.stream_ptr(dev), ev0, ev1, _lib.ptr(score_range))
-    _lib.check(rc, "halo_score_maps")
+    ev0, ev1 = events if events is not None else (None, None)
+    _run_scorer(_lib.SCORE_FULL, logit, feat, (H, W), gt, act, (score, imp, unc), unc_type=unc_type, pur_type=pur_type,
+                flags=_lib.score_flags(normalize, padding_mode), ksize=size, psize=size if purity_size is None else purity_size,
+                K=K, c=c, events={"ev_feat_start": ev0, "ev_feat_stop": ev1}, score_range=score_range, tail_stream=tail_stream,
+                workspace=workspace)
     return score, imp, unc
 
 
@@ -207,51 +220,27 @@ def score_maps_lowres(logit_lr, decoder_lr, size, unc_type=None, pur_type=None, 
     dev = _lib.require_device(logit_lr, decoder_lr, ground_truth, active)
     H, W = int(size[0]), int(size[1])
     logit_lr = logit_lr.float().contiguous()
-    B, O, hl, wl = logit_lr.shape
+    B = logit_lr.shape[0]
     need_feat = pur_type in ("hyper", "radius", "euc_norm")
-    feat, Cc, fdt, fbs, hf, wf = None, 0, _lib.F64, 0, 0, 0
+    feat = None
     if need_feat:
         if decoder_lr is None:
             raise ValueError("decoder_out is required for purity type '%s'" % pur_type)
         feat = decoder_lr if decoder_lr.dtype in (torch.float32, torch.float64) else decoder_lr.float()
         feat = feat.contiguous()
         assert feat.shape[0] == B
-        Cc, hf, wf = feat.shape[1:]
-        fdt, fbs = _lib.dtype_code(feat), feat.stride(0)
-    need_gt = unc_type == "oracle_acc" or pur_type == "oracle_ripu"
-    if need_gt and ground_truth is None:
-        raise ValueError("ground_truth is required for '%s'/'%s'" % (unc_type, pur_type))
-    gt = ground_truth.reshape(B, H, W).to(torch.int64).contiguous() if need_gt else None
-    act = None
-    if active is not None:
-        act = active.reshape(B, H, W).contiguous()
-        act = act.view(torch.uint8) if act.dtype == torch.bool else act.to(torch.uint8)
+    gt, act = _labels_and_mask(unc_type, pur_type, ground_truth, active, (B, H, W))
     odt = score_dtype(pur_type, feat)
     score = torch.empty((B, H, W), dtype=odt, device=dev)
     imp = torch.empty((B, H, W), dtype=odt, device=dev) if want_maps else None
     unc = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_maps else None
-    L = _lib.lib()
-    gram = mode == "gram" and need_feat and fdt == _lib.F64
-    nws = L.halo_score_lr_gram_workspace_bytes(B, O, H, W, hf, wf) if gram else L.halo_score_lr_workspace_bytes(B, O, H, W)
-    ws = _workspace(dev, nws, "score")
-    psize = ksize if purity_size is None else purity_size
-    fn, name = (L.halo_score_maps_lr_gram, "halo_score_maps_lr_gram") if gram else (L.halo_score_maps_lr, "halo_score_maps_lr")
-    args = (_lib.ptr(logit_lr), logit_lr.stride(0), hl, wl, _lib.ptr(feat), fdt, fbs, hf, wf,
-            _lib.ptr(gt), _lib.ptr(act), B, O, Cc, H, W, _lib.UNC.get(unc_type, _lib.UNC_ZEROS),
-            _lib.PUR[pur_type], _lib.score_flags(normalize, padding_mode), int(ksize), int(psize), int(K), float(c),
-            _lib.ptr(score), _lib.ptr(imp), _lib.ptr(unc), _lib.ptr(ws), ws.numel(),
-            _lib.stream_ptr(dev))
-    if events is not None or score_range is not None:
-        # events: (logit start, logit stop, embedding start, embedding stop[, embedding mid (gram: between the Gram pass and the
-        # radius pass), tail stop]) from halo_event_create, or None each
-        if score_range is not None:
-            assert score_range.is_contiguous() and score_range.device == dev and score_range.numel() >= L.halo_score_range_bytes(B)
-        name = "halo_score_maps_lr_timed"
-        ev = tuple(events or ()) + (None,) * 6
-        rc = L.halo_score_maps_lr_timed(*(args + (1 if gram else 0,) + ev[:4] + (_lib.ptr(score_range),) + ev[4:6]))
-    else:
-        rc = fn(*args)
-    _lib.check(rc, name)
+    gram = mode == "gram" and need_feat and feat.dtype == torch.float64
+    # events: (logit start, logit stop, embedding start, embedding stop[, embedding mid (gram: between the Gram pass and the
+    # radius pass), tail stop]) from halo_event_create, or None each
+    ev = dict(zip(("ev_logit_start", "ev_logit_stop", "ev_feat_start", "ev_feat_stop", "ev_feat_mid", "ev_tail_stop"), events or ()))
+    _run_scorer(_lib.SCORE_LR_GRAM if gram else _lib.SCORE_LR, logit_lr, feat, (H, W), gt, act, (score, imp, unc),
+                unc_type=unc_type, pur_type=pur_type, flags=_lib.score_flags(normalize, padding_mode), ksize=ksize,
+                psize=ksize if purity_size is None else purity_size, K=K, c=c, events=ev, score_range=score_range)
     return score, imp, unc
 
 

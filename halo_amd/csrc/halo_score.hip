@@ -635,7 +635,7 @@ __global__ void __launch_bounds__(TPB) k_region_impurity3(const TL *__restrict__
 // Returns the number of min/max partials per image written to `partials` (0: none -- the caller runs k_minmax_f32).
 template <typename TL>
 static int launch_region_impurity(const TL *pred, int64_t B, int64_t H, int64_t W, int k, float logK, float *imp, float *count,
-                                  hipStream_t st, double *partials = nullptr, int pad = HALO_PAD_ZEROS)
+                                  hipStream_t st, double *partials, int pad)
 {
     if (pad == HALO_PAD_ZEROS && k == 3 && cdiv(H, RI_TH) <= 65535 && B <= 65535) {
         const dim3 grid((unsigned)cdiv(W, RI_TW), (unsigned)cdiv(H, RI_TH), (unsigned)B);
@@ -1830,7 +1830,7 @@ __global__ void __launch_bounds__(TPB, (PPT > LR_PPT ? HALO_LR8_WAVES : 1)) k_fe
 // k_gram_lr computes the maps in one pass over the low-res tensor (sequential fma chains over the channels);
 // k_radius_gram evaluates the 10-term form per output pixel.  Mathematically the same number as k_feat_reduce_lr,
 // rounded differently (a few 1e-16 of the largest corner norm; pixels whose terms cancel take the exact order: GRAM_GUARD),
-// so this mode is NOT bit-identical to upsample-then-score: it is opt-in (halo_score_maps_lr_gram) and float64 only.
+// so this mode is NOT bit-identical to upsample-then-score: it is opt-in (HALO_SCORE_LR_GRAM) and float64 only.
 constexpr int GRAM_MAPS = 5;
 constexpr int GRAM_COLS = 63;          // columns per wave: lane 63 only supplies the right neighbour of lane 62
 
@@ -2116,7 +2116,7 @@ struct FusedLogit { const float *logit; long long bstride; int O; int unc_type; 
 
 template <typename T, int VEC>
 static void launch_feat(const T *feat, long long bstride, int C, long long hw, int B, int mode, double ks, double rks,
-                        T *out, double *partials, int nblk, hipStream_t st, const FusedLogit *fl = nullptr)
+                        T *out, double *partials, int nblk, hipStream_t st, const FusedLogit *fl)
 {
     dim3 grid(nblk, B), block(FTPB);
     constexpr int UNROLL = HALO_FEAT_UNROLL;      // channel planes in flight per lane (16: no gain beside the selection kernels, 6 % slower alone)
@@ -2165,33 +2165,39 @@ extern "C" size_t halo_score_workspace_bytes(int64_t B, int64_t H, int64_t W)
     return s + 1024;
 }
 
-extern "C" int halo_score_maps(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                               int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                               int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                               int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                               void *workspace, size_t workspace_bytes, void *stream)
+extern "C" size_t halo_score_args_workspace_bytes(const halo_score_args *a)
 {
-    return halo_score_maps_timed(logit, logit_bstride, feat, feat_dtype, feat_bstride, gt, active, B, O, C, H, W, unc_type,
-                                 pur_type, normalize, ksize, pksize, K, c, score, impurity, uncertainty, workspace,
-                                 workspace_bytes, stream, nullptr, nullptr, nullptr);
+    if (!a || a->struct_bytes != sizeof(halo_score_args)) return 0;
+    size_t s = halo_score_workspace_bytes(a->B, a->H, a->W);
+    if (s == 0 || a->route == HALO_SCORE_FULL) return s;
+    if (a->route != HALO_SCORE_LR && a->route != HALO_SCORE_LR_GRAM) return 0;
+    if (a->O <= 0) return 0;
+    if (!(a->O == 19 || a->O == 16)) s += (size_t)a->B * a->O * a->H * a->W * 4 + 512;       // the upsampled logits of a generic class count
+    if (a->route == HALO_SCORE_LR) return s;
+    if (a->hf <= 0 || a->wf <= 0) return 0;
+    return s + (size_t)a->B * 5 * a->hf * a->wf * 8 + 512;                                    // the 5 Gram maps over the low-res grid
 }
 
-extern "C" size_t halo_score_lr_workspace_bytes(int64_t B, int64_t O, int64_t H, int64_t W)
-{
-    const size_t base = halo_score_workspace_bytes(B, H, W);
-    if (base == 0 || O <= 0) return 0;
-    return base + ((O == 19 || O == 16) ? 0 : (size_t)B * O * H * W * 4 + 512);
-}
+static inline bool reads_feat(int pur_type) { return pur_type == HALO_PUR_HYPER || pur_type == HALO_PUR_RADIUS || pur_type == HALO_PUR_EUC_NORM; }
+static inline bool is_ripu(int pur_type) { return pur_type == HALO_PUR_RIPU || pur_type == HALO_PUR_ORACLE_RIPU; }
+static inline void record(void *event, hipStream_t st) { if (event) (void)hipEventRecord((hipEvent_t)event, st); }
 
-extern "C" size_t halo_score_lr_gram_workspace_bytes(int64_t B, int64_t O, int64_t H, int64_t W, int64_t hf, int64_t wf)
-{
-    const size_t base = halo_score_lr_workspace_bytes(B, O, H, W);
-    if (base == 0 || hf <= 0 || wf <= 0) return 0;
-    return base + (size_t)B * 5 * hf * wf * 8 + 512;
-}
-
-// low-res source geometry (halo_score_maps_lr); gram: the embedding's radius through the Gram form (float64 only)
-struct LrDims { int hl, wl, hf, wf; bool gram; };
+// What the phases of score_impl share: the carved workspace, the decisions every phase reads, and the block counts of the
+// min / max partials one phase hands the next.
+struct ScorePlan {
+    float *ent, *unc_raw;
+    double *imp_raw;
+    short *pred;
+    double *part_imp, *part_unc, *stats;
+    float *lr_logit_full;           // low-res routes, class counts other than 19 / 16: the upsampled logits
+    double *gram;                   // Gram route: the 5 inner-product maps over the low-res grid
+    bool lr, need_feat, hist, f64out, fuse;
+    int pad, normalize, mode;       // padding mode and bit 0 of the flags word; mode 0 = radius, 1 = Euclidean norm
+    double ks, rks;
+    long long hw;
+    int nblk1, nblk_imp, nblk_unc;
+    FusedLogit fl;                  // the logit pass inside k_feat_reduce (`fuse`)
+};
 
 template <typename T>
 static void lr_window(int out_size, int in_size, int tile, int &max_span)
@@ -2207,14 +2213,19 @@ static void lr_window(int out_size, int in_size, int tile, int &max_span)
 }
 
 template <typename T>
-static int launch_feat_lr(const T *feat, long long bstride, int C, const LrDims &lr, int H, int W, int B, int mode, double ks,
-                          double rks, T *out, double *partials, int &nblk, hipStream_t st)
+static int launch_feat_lr(const halo_score_args &a, ScorePlan &p, T *out, hipStream_t st)
 {
+    const T *feat = (const T *)a.feat;
+    const long long bstride = a.feat_bstride;
+    const int C = (int)a.C, hf = (int)a.hf, wf = (int)a.wf, H = (int)a.H, W = (int)a.W, B = (int)a.B, mode = p.mode;
+    const double ks = p.ks, rks = p.rks;
+    double *partials = p.part_imp;
+    int &nblk = p.nblk_imp;       // min / max partials per image: one per workgroup of the kernel chosen below
     int max_rows, max_cols;
-    lr_window<T>(H, lr.hf, LR_TH, max_rows);
-    lr_window<T>(W, lr.wf, LR_TW, max_cols);
+    lr_window<T>(H, hf, LR_TH, max_rows);
+    lr_window<T>(W, wf, LR_TW, max_cols);
     ++max_rows; ++max_cols;       // the staged window carries one clamped extra row and column (k_feat_reduce_lr)
-    const T sh = H > 1 ? (T)(lr.hf - 1) / (T)(H - 1) : (T)0, sw = W > 1 ? (T)(lr.wf - 1) / (T)(W - 1) : (T)0;
+    const T sh = H > 1 ? (T)(hf - 1) / (T)(H - 1) : (T)0, sw = W > 1 ? (T)(wf - 1) / (T)(W - 1) : (T)0;
     dim3 grid((unsigned)cdiv(W, LR_TW), (unsigned)cdiv(H, LR_TH), (unsigned)B), block(TPB);
     nblk = (int)(grid.x * grid.y);
     if constexpr (sizeof(T) == 8) {
@@ -2223,7 +2234,7 @@ static int launch_feat_lr(const T *feat, long long bstride, int C, const LrDims 
         const int units_per_ch = max_rows * ((max_cols + 2) / 2 + 1);        // even start column: up to one more pair per row
         int CCd = DMA_UNITS / units_per_ch;
         CCd = CCd > C ? C : CCd;
-        const bool dma_ok = lr.wf >= 2 && lr.wf % 2 == 0 && bstride % 2 == 0 && aligned16(feat) && CCd >= 4;
+        const bool dma_ok = wf >= 2 && wf % 2 == 0 && bstride % 2 == 0 && aligned16(feat) && CCd >= 4;
         if (dma_ok) {
             const size_t lds = 2 * (size_t)DMA_UNITS * 16;
             // compile-time image geometries (k_feat_reduce_lr_dmaf): rows x pairs that cover the launch's largest window
@@ -2232,14 +2243,14 @@ static int launch_feat_lr(const T *feat, long long bstride, int C, const LrDims 
             // is instantiated for (HALO_LR_CODES8) then cover every wave; otherwise the 4-pixel kernel (same bits)
             if ((double)sh <= 1.0 / 3.0 && H >= 2 * LR_TH) {
                 int max_rows8;
-                lr_window<T>(H, lr.hf, 2 * LR_TH, max_rows8);
+                lr_window<T>(H, hf, 2 * LR_TH, max_rows8);
                 ++max_rows8;
                 dim3 grid8((unsigned)cdiv(W, LR_TW), (unsigned)cdiv(H, 2 * LR_TH), (unsigned)B);
 #define HALO_LR_FIXED8(R_, U_)                                                                                                             \
                 if (max_rows8 <= R_ && need_u <= U_) {                                                                                     \
                     nblk = (int)(grid8.x * grid8.y);                                                                                       \
-                    if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
-                    else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
+                    if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
+                    else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
                     return HALO_OK;                                                                                                        \
                 }
                 HALO_LR_FIXED8(8, 8)       // x6.4 (160x320 -> 1024x2048): 16 channels per image
@@ -2248,28 +2259,28 @@ static int launch_feat_lr(const T *feat, long long bstride, int C, const LrDims 
             }
 #define HALO_LR_FIXED(R_, U_)                                                                                                              \
             if (need_rows <= R_ && need_u <= U_) {                                                                                         \
-                if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
-                else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
+                if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
+                else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
                 return HALO_OK;                                                                                                            \
             }
             HALO_LR_FIXED(6, 8)        // x6.4 (160x320 -> 1024x2048): 21 channels per image
             HALO_LR_FIXED(7, 10)       // x4: 14 channels per image
             HALO_LR_FIXED(8, 12)
 #undef HALO_LR_FIXED
-            if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dma<0>), grid, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials);
-            else hipLaunchKernelGGL((k_feat_reduce_lr_dma<1>), grid, block, lds, st, (const double *)feat, bstride, C, lr.hf, lr.wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials);
+            if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dma<0>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials);
+            else hipLaunchKernelGGL((k_feat_reduce_lr_dma<1>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials);
             return HALO_OK;
         }
     }
     const size_t plane_bytes = (size_t)max_rows * max_cols * sizeof(T);
-    if (plane_bytes > 48 * 1024) return fail(HALO_E_UNSUPPORTED, "halo_score_maps_lr: source window too large for LDS (downsampling?)");
+    if (plane_bytes > 48 * 1024) return fail(HALO_E_UNSUPPORTED, "halo_score: source window too large for LDS (downsampling?)");
     // channels per chunk: what the block's four waves prefetch in one group each (k_feat_reduce_lr), LDS permitting
     int CC = (int)((48 * 1024) / plane_bytes);
     CC = CC > (TPB / 64) * LR_STAGE_G ? (TPB / 64) * LR_STAGE_G : CC;
     CC = CC > C ? C : CC;
     const size_t lds = (size_t)CC * plane_bytes;
-    if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr<T, 0>), grid, block, lds, st, feat, bstride, C, lr.hf, lr.wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials);
-    else hipLaunchKernelGGL((k_feat_reduce_lr<T, 1>), grid, block, lds, st, feat, bstride, C, lr.hf, lr.wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials);
+    if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr<T, 0>), grid, block, lds, st, feat, bstride, C, hf, wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials);
+    else hipLaunchKernelGGL((k_feat_reduce_lr<T, 1>), grid, block, lds, st, feat, bstride, C, hf, wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials);
     return HALO_OK;
 }
 
@@ -2285,231 +2296,287 @@ static int check_padding(int pad, int k, int64_t H, int64_t W, const char *who)
     return HALO_OK;
 }
 
-static int score_impl(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                      int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                      int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                      int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                      void *workspace, size_t workspace_bytes, void *stream, void *ev_feat_start,
-                      void *ev_feat_stop, const LrDims *lr, void *ev_logit_start = nullptr, void *ev_logit_stop = nullptr,
-                      void *score_range = nullptr, void *tail_stream = nullptr, void *ev_feat_mid = nullptr, void *ev_tail_stop = nullptr)
+// The argument checks of halo_score, in the order the entry points have always made them: the first failure is the one reported.
+static int check_score_args(const halo_score_args &a)
 {
-    hipStream_t st = (hipStream_t)stream;
-    // `normalize` is the flags word of include/halo_hip.h: bit 0 = normalise, bits 8-9 = padding mode of the two box windows
-    const int pad = (normalize >> 8) & 3;
-    if (normalize & ~(HALO_FLAG_NORMALIZE | (3 << 8))) return fail(HALO_E_ARG, "halo_score_maps: unknown flag bits 0x%x", normalize);
-    normalize &= HALO_FLAG_NORMALIZE;
-    if (!logit || !score || B <= 0 || O <= 0 || H <= 0 || W <= 0) return fail(HALO_E_ARG, "halo_score_maps: null/empty argument");
-    if (unc_type < 0 || unc_type > HALO_UNC_ZEROS) return fail(HALO_E_ARG, "halo_score_maps: bad unc_type %d", unc_type);
-    if (pur_type < 0 || pur_type > HALO_PUR_EUC_NORM) return fail(HALO_E_UNSUPPORTED, "Error: purity type '%d' not implemented", pur_type);
-    if (ksize < 1 || !(ksize & 1) || pksize < 1 || !(pksize & 1)) return fail(HALO_E_ARG, "halo_score_maps: window sizes must be odd");
-    {
-        const int rc = check_padding(pad, ksize > pksize ? ksize : pksize, H, W, "halo_score_maps");
-        if (rc != HALO_OK) return rc;
+    if (a.struct_bytes != sizeof(halo_score_args))
+        return fail(HALO_E_ARG, "halo_score: descriptor of %zu bytes, this library reads %zu (another ABI?)", a.struct_bytes, sizeof(halo_score_args));
+    if (a.route < HALO_SCORE_FULL || a.route > HALO_SCORE_LR_GRAM) return fail(HALO_E_ARG, "halo_score: unknown route %d", a.route);
+    const bool need_feat = reads_feat(a.pur_type);
+    if (a.route != HALO_SCORE_FULL) {
+        if (a.hl <= 0 || a.wl <= 0) return fail(HALO_E_ARG, "halo_score: bad low-res logit size");
+        if (need_feat && (a.hf <= 0 || a.wf <= 0)) return fail(HALO_E_ARG, "halo_score: bad low-res embedding size");
     }
-    const bool need_feat = pur_type == HALO_PUR_HYPER || pur_type == HALO_PUR_RADIUS || pur_type == HALO_PUR_EUC_NORM;
-    if (need_feat && (!feat || C <= 0)) return fail(HALO_E_ARG, "halo_score_maps: decoder_out required for this purity type");
-    if (need_feat && feat_dtype != HALO_F32 && feat_dtype != HALO_F64) return fail(HALO_E_ARG, "halo_score_maps: bad feat dtype");
-    const bool need_gt = unc_type == HALO_UNC_ORACLE_ACC || pur_type == HALO_PUR_ORACLE_RIPU;
-    if (need_gt && !gt) return fail(HALO_E_ARG, "halo_score_maps: ground_truth required");
-    if (pur_type == HALO_PUR_HYPER && (K < 1 || K > 32767)) return fail(HALO_E_UNSUPPORTED, "halo_score_maps: K out of range");
-    if (O > 32767) return fail(HALO_E_UNSUPPORTED, "halo_score_maps: too many classes");
-    if (workspace_bytes < halo_score_workspace_bytes(B, H, W) || !workspace) return fail(HALO_E_WORKSPACE, "halo_score_maps: workspace too small");
-    const bool lr_generic_O = lr && !(O == 19 || O == 16);
-    if (lr_generic_O && workspace_bytes < halo_score_workspace_bytes(B, H, W) + (size_t)B * O * H * W * 4 + 256)
-        return fail(HALO_E_WORKSPACE, "halo_score_maps_lr: workspace too small for %d classes", (int)O);
+    if (a.route == HALO_SCORE_LR_GRAM && need_feat) {
+        if (a.hf * a.wf > 0x7fffffffll) return fail(HALO_E_UNSUPPORTED, "halo_score: low-res planes of more than 2^31 elements (Gram route)");
+        if (a.workspace_bytes < halo_score_args_workspace_bytes(&a)) return fail(HALO_E_WORKSPACE, "halo_score: workspace too small for the Gram route");
+    }
+    if (a.flags & ~(HALO_FLAG_NORMALIZE | (3 << 8))) return fail(HALO_E_ARG, "halo_score: unknown flag bits 0x%x", a.flags);
+    if (!a.logit || !a.score || a.B <= 0 || a.O <= 0 || a.H <= 0 || a.W <= 0) return fail(HALO_E_ARG, "halo_score: null/empty argument");
+    if (a.unc_type < 0 || a.unc_type > HALO_UNC_ZEROS) return fail(HALO_E_ARG, "halo_score: bad unc_type %d", a.unc_type);
+    if (a.pur_type < 0 || a.pur_type > HALO_PUR_EUC_NORM) return fail(HALO_E_UNSUPPORTED, "Error: purity type '%d' not implemented", a.pur_type);
+    if (a.ksize < 1 || !(a.ksize & 1) || a.pksize < 1 || !(a.pksize & 1)) return fail(HALO_E_ARG, "halo_score: window sizes must be odd");
+    const int rc = check_padding((a.flags >> 8) & 3, a.ksize > a.pksize ? a.ksize : a.pksize, a.H, a.W, "halo_score");
+    if (rc != HALO_OK) return rc;
+    if (need_feat && (!a.feat || a.C <= 0)) return fail(HALO_E_ARG, "halo_score: decoder_out required for this purity type");
+    if (need_feat && a.feat_dtype != HALO_F32 && a.feat_dtype != HALO_F64) return fail(HALO_E_ARG, "halo_score: bad feat dtype");
+    const bool need_gt = a.unc_type == HALO_UNC_ORACLE_ACC || a.pur_type == HALO_PUR_ORACLE_RIPU;
+    if (need_gt && !a.gt) return fail(HALO_E_ARG, "halo_score: ground_truth required");
+    if (a.pur_type == HALO_PUR_HYPER && (a.K < 1 || a.K > 32767)) return fail(HALO_E_UNSUPPORTED, "halo_score: K out of range");
+    if (a.O > 32767) return fail(HALO_E_UNSUPPORTED, "halo_score: too many classes");
+    const size_t base = halo_score_workspace_bytes(a.B, a.H, a.W);
+    if (a.workspace_bytes < base || !a.workspace) return fail(HALO_E_WORKSPACE, "halo_score: workspace too small");
+    if (a.route != HALO_SCORE_FULL && !(a.O == 19 || a.O == 16) && a.workspace_bytes < base + (size_t)a.B * a.O * a.H * a.W * 4 + 256)
+        return fail(HALO_E_WORKSPACE, "halo_score: workspace too small for %d classes from low-res logits", (int)a.O);
+    return HALO_OK;
+}
 
-    const long long hw = (long long)H * W;
-    const int nblk1 = (int)cdiv(hw, TPB);
-    Arena ar(workspace, workspace_bytes);
-    float *ent = ar.take<float>((size_t)B * hw);
-    float *unc_raw = ar.take<float>((size_t)B * hw);
-    double *imp_raw = ar.take<double>((size_t)B * hw);
-    short *pred = ar.take<short>((size_t)B * hw);
-    double *part_imp = ar.take<double>((size_t)B * partial_slots(H, W) * 2);
-    double *part_unc = ar.take<double>((size_t)B * partial_slots(H, W) * 2);
-    double *stats = ar.take<double>((size_t)B * 4);
-    float *lr_logit_full = lr_generic_O ? ar.take<float>((size_t)B * O * hw) : nullptr;
-    const bool gram_mode = lr && lr->gram && need_feat;
-    if (gram_mode && feat_dtype != HALO_F64) return fail(HALO_E_UNSUPPORTED, "halo_score_maps_lr_gram: float64 embeddings only");
-    double *gram = gram_mode ? ar.take<double>((size_t)B * GRAM_MAPS * lr->hf * lr->wf) : nullptr;
-    if (!ar.ok()) return fail(HALO_E_WORKSPACE, "halo_score_maps: workspace too small");
+// Carve the workspace and take the decisions more than one phase reads.
+static int make_score_plan(const halo_score_args &a, ScorePlan &p)
+{
+    const size_t B = (size_t)a.B;
+    p.lr = a.route != HALO_SCORE_FULL;
+    p.need_feat = reads_feat(a.pur_type);
+    p.pad = (a.flags >> 8) & 3;
+    p.normalize = a.flags & HALO_FLAG_NORMALIZE;
+    p.hw = (long long)a.H * a.W;
+    p.nblk1 = (int)cdiv(p.hw, TPB);
+    p.nblk_imp = p.nblk_unc = p.nblk1;
 
-    const bool f64out = (pur_type == HALO_PUR_RADIUS || pur_type == HALO_PUR_EUC_NORM) && feat_dtype == HALO_F64;
-    const bool hist = pur_type == HALO_PUR_RIPU || pur_type == HALO_PUR_ORACLE_RIPU || pur_type == HALO_PUR_HYPER;
-    const double ks = sqrt(fabs(-c) + 1e-15), rks = 1.0 / ks;
-    dim3 block(TPB);
+    Arena ar(a.workspace, a.workspace_bytes);
+    p.ent = ar.take<float>(B * p.hw);
+    p.unc_raw = ar.take<float>(B * p.hw);
+    p.imp_raw = ar.take<double>(B * p.hw);
+    p.pred = ar.take<short>(B * p.hw);
+    p.part_imp = ar.take<double>(B * partial_slots(a.H, a.W) * 2);
+    p.part_unc = ar.take<double>(B * partial_slots(a.H, a.W) * 2);
+    p.stats = ar.take<double>(B * 4);
+    p.lr_logit_full = (p.lr && !(a.O == 19 || a.O == 16)) ? ar.take<float>(B * a.O * p.hw) : nullptr;
+    const bool gram_mode = a.route == HALO_SCORE_LR_GRAM && p.need_feat;
+    if (gram_mode && a.feat_dtype != HALO_F64) return fail(HALO_E_UNSUPPORTED, "halo_score: float64 embeddings only on the Gram route");
+    p.gram = gram_mode ? ar.take<double>(B * GRAM_MAPS * a.hf * a.wf) : nullptr;
+    if (!ar.ok()) return fail(HALO_E_WORKSPACE, "halo_score: workspace too small");
 
-    // ---- logits -> ent (+ pred for ripu / oracle_ripu); fused into the feature stream when possible
-    const bool ent_only = (unc_type == HALO_UNC_ENTROPY || unc_type == HALO_UNC_PIXEL_ENTROPY) &&
-                          pur_type != HALO_PUR_RIPU && pur_type != HALO_PUR_ORACLE_RIPU;
-    const int fvec = !need_feat ? 0 : (feat_dtype == HALO_F64
-        ? (((hw % 2 == 0) && (feat_bstride % 2 == 0) && aligned16(feat) && aligned16(imp_raw)) ? 2 : 1)
-        : (((hw % 4 == 0) && (feat_bstride % 4 == 0) && aligned16(feat) && aligned16(imp_raw)) ? 4 : 1));
-    const bool fuse = !lr && need_feat && ent_only && (O == 19 || O == 16) && fvec > 1 && (logit_bstride % fvec == 0) &&
-                      (((uintptr_t)logit) % (4 * fvec) == 0);
-    FusedLogit fl{logit, (long long)logit_bstride, (int)O, unc_type, ent};
-    const FusedLogit *flp = fuse ? &fl : nullptr;
-    const bool need_logit_pass = !fuse && ( unc_type != HALO_UNC_ZEROS || pur_type == HALO_PUR_RIPU || pur_type == HALO_PUR_ORACLE_RIPU);
-    short *pred_from_logits = (pur_type == HALO_PUR_RIPU || pur_type == HALO_PUR_ORACLE_RIPU) ? pred : nullptr;
-    if (ev_logit_start) (void)hipEventRecord((hipEvent_t)ev_logit_start, st);
-    if (need_logit_pass && lr) {
-        const float shl = H > 1 ? (float)(lr->hl - 1) / (float)(H - 1) : 0.0f, swl = W > 1 ? (float)(lr->wl - 1) / (float)(W - 1) : 0.0f;
-        dim3 grid((unsigned)nblk1, (unsigned)B);
+    p.f64out = (a.pur_type == HALO_PUR_RADIUS || a.pur_type == HALO_PUR_EUC_NORM) && a.feat_dtype == HALO_F64;
+    p.hist = is_ripu(a.pur_type) || a.pur_type == HALO_PUR_HYPER;
+    p.mode = a.pur_type == HALO_PUR_EUC_NORM ? 1 : 0;
+    p.ks = sqrt(fabs(-a.c) + 1e-15);
+    p.rks = 1.0 / p.ks;
+
+    // logits -> ent inside the feature stream (k_feat_reduce's FO variants) when the full-res route allows it
+    const bool ent_only = (a.unc_type == HALO_UNC_ENTROPY || a.unc_type == HALO_UNC_PIXEL_ENTROPY) && !is_ripu(a.pur_type);
+    const int fvec = !p.need_feat ? 0 : (a.feat_dtype == HALO_F64
+        ? (((p.hw % 2 == 0) && (a.feat_bstride % 2 == 0) && aligned16(a.feat) && aligned16(p.imp_raw)) ? 2 : 1)
+        : (((p.hw % 4 == 0) && (a.feat_bstride % 4 == 0) && aligned16(a.feat) && aligned16(p.imp_raw)) ? 4 : 1));
+    p.fuse = !p.lr && p.need_feat && ent_only && (a.O == 19 || a.O == 16) && fvec > 1 && (a.logit_bstride % fvec == 0) &&
+             (((uintptr_t)a.logit) % (4 * fvec) == 0);
+    p.fl = FusedLogit{a.logit, (long long)a.logit_bstride, (int)a.O, a.unc_type, p.ent};
+    return HALO_OK;
+}
+
+// ---- logits -> ent (+ pred for ripu / oracle_ripu); nothing when the feature pass carries them (p.fuse)
+static void launch_logit_pass(const halo_score_args &a, const ScorePlan &p, hipStream_t st)
+{
+    if (p.fuse) return;
+    const int B = (int)a.B, O = (int)a.O, H = (int)a.H, W = (int)a.W;
+    const long long hw = p.hw, bstride = a.logit_bstride;
+    const long long *gt = (const long long *)a.gt;
+    short *pred = is_ripu(a.pur_type) ? p.pred : nullptr;
+    const dim3 block(TPB), grid1((unsigned)p.nblk1, (unsigned)B);
+    if (a.unc_type == HALO_UNC_ZEROS && !is_ripu(a.pur_type)) {
+        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)cdiv(B * hw, TPB)), block, 0, st, p.ent, (long long)(B * hw), 0.0f);
+    } else if (p.lr) {
+        const int hl = (int)a.hl, wl = (int)a.wl;
+        const float shl = H > 1 ? (float)(hl - 1) / (float)(H - 1) : 0.0f, swl = W > 1 ? (float)(wl - 1) / (float)(W - 1) : 0.0f;
         if (O == 19)
-            hipLaunchKernelGGL((k_logit_maps_lr<19>), grid, block, 0, st, logit, (long long)logit_bstride, lr->hl, lr->wl, (int)H, (int)W, shl, swl, (const long long *)gt, unc_type, pur_type, ent, pred_from_logits);
+            hipLaunchKernelGGL((k_logit_maps_lr<19>), grid1, block, 0, st, a.logit, bstride, hl, wl, H, W, shl, swl, gt, a.unc_type, a.pur_type, p.ent, pred);
         else if (O == 16)
-            hipLaunchKernelGGL((k_logit_maps_lr<16>), grid, block, 0, st, logit, (long long)logit_bstride, lr->hl, lr->wl, (int)H, (int)W, shl, swl, (const long long *)gt, unc_type, pur_type, ent, pred_from_logits);
+            hipLaunchKernelGGL((k_logit_maps_lr<16>), grid1, block, 0, st, a.logit, bstride, hl, wl, H, W, shl, swl, gt, a.unc_type, a.pur_type, p.ent, pred);
         else {
-            hipLaunchKernelGGL(k_logit_interp_lr, grid, block, 0, st, logit, (long long)logit_bstride, (int)O, lr->hl, lr->wl, (int)H, (int)W, shl, swl, lr_logit_full);
-            hipLaunchKernelGGL(k_logit_maps_generic, grid, block, 0, st, (const float *)lr_logit_full, (long long)(O * hw), (const long long *)gt, (int)O, hw, unc_type, pur_type, 0, ent, pred_from_logits);
+            hipLaunchKernelGGL(k_logit_interp_lr, grid1, block, 0, st, a.logit, bstride, O, hl, wl, H, W, shl, swl, p.lr_logit_full);
+            hipLaunchKernelGGL(k_logit_maps_generic, grid1, block, 0, st, (const float *)p.lr_logit_full, (long long)(O * hw), gt, O, hw, a.unc_type, a.pur_type, 0, p.ent, pred);
         }
-    } else if (need_logit_pass) {
-        const bool vec4 = (hw % 4 == 0) && (logit_bstride % 4 == 0) && aligned16(logit) && aligned16(ent);
-        if (O == 19 && vec4) {
-            dim3 grid((unsigned)cdiv(hw, TPB * 4), (unsigned)B);
-            hipLaunchKernelGGL((k_logit_maps<19, 4>), grid, block, 0, st, logit, (long long)logit_bstride, (const long long *)gt, hw, unc_type, pur_type, ent, pred_from_logits);
-        } else if (O == 16 && vec4) {
-            dim3 grid((unsigned)cdiv(hw, TPB * 4), (unsigned)B);
-            hipLaunchKernelGGL((k_logit_maps<16, 4>), grid, block, 0, st, logit, (long long)logit_bstride, (const long long *)gt, hw, unc_type, pur_type, ent, pred_from_logits);
-        } else {
-            dim3 grid((unsigned)nblk1, (unsigned)B);
-            hipLaunchKernelGGL(k_logit_maps_generic, grid, block, 0, st, logit, (long long)logit_bstride, (const long long *)gt, (int)O, hw, unc_type, pur_type, 0, ent, pred_from_logits);
-        }
-    } else if (!fuse) {
-        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)cdiv(B * hw, TPB)), block, 0, st, ent, (long long)(B * hw), 0.0f);
+    } else {
+        const bool vec4 = (hw % 4 == 0) && (bstride % 4 == 0) && aligned16(a.logit) && aligned16(p.ent);
+        const dim3 grid4((unsigned)cdiv(hw, TPB * 4), (unsigned)B);
+        if (O == 19 && vec4)
+            hipLaunchKernelGGL((k_logit_maps<19, 4>), grid4, block, 0, st, a.logit, bstride, gt, hw, a.unc_type, a.pur_type, p.ent, pred);
+        else if (O == 16 && vec4)
+            hipLaunchKernelGGL((k_logit_maps<16, 4>), grid4, block, 0, st, a.logit, bstride, gt, hw, a.unc_type, a.pur_type, p.ent, pred);
+        else
+            hipLaunchKernelGGL(k_logit_maps_generic, grid1, block, 0, st, a.logit, bstride, gt, O, hw, a.unc_type, a.pur_type, 0, p.ent, pred);
     }
+}
 
-    if (ev_logit_stop) (void)hipEventRecord((hipEvent_t)ev_logit_stop, st);
-
-    // ---- features -> radius / norm  (+ min/max partials)
-    int nblk_imp = nblk1;
-    if (need_feat) {
-        if (ev_feat_start) (void)hipEventRecord((hipEvent_t)ev_feat_start, st);
-        const int mode = pur_type == HALO_PUR_EUC_NORM ? 1 : 0;
-        if (gram_mode) {
-            // 16 bytes per lane where the planes allow it (even width, 16-byte aligned); otherwise the 8-byte kernel
-            const bool wide = lr->wf >= 2 && lr->wf % 2 == 0 && feat_bstride % 2 == 0 && aligned16(feat) && aligned16(gram);
-            if (wide) {
-                // rows per wave: every source row is loaded (R + 1) / R times (its own strip + as lower neighbour of the strip above),
-                // and that redundancy, not the bytes in flight, is what the kernel's time follows (profiles/archive/r04_gram_ab.txt: R = 2 / 4 /
-                // 8 -> 788 / 745 / 705 us per 16 images; 2, 3 or 4 channels in flight: equal; non-temporal loads: 20 % slower).  The
-                // widest strip that still gives every SIMD of the chip a wave; one channel in flight for 8-row strips, two otherwise
-                const long long nwx = cdiv(lr->wf, 128);
-                int rows = 2;
-                for (int cand = 8; cand > 2; cand >>= 1)
-                    if (B * nwx * cdiv(lr->hf, cand) >= 1024) { rows = cand; break; }
-                const long long nwaves = nwx * cdiv(lr->hf, rows);
-                const dim3 gg((unsigned)(cdiv(cdiv(nwaves, TPB / 64), 8) * 8), (unsigned)B);
-#define HALO_GRAM2(U_, R_) hipLaunchKernelGGL((k_gram_lr2<U_, R_>), gg, block, 0, st, (const double *)feat, (long long)feat_bstride, (int)C, lr->hf, lr->wf, gram)
-                if (rows == 8) HALO_GRAM2(1, 8);
-                else if (rows == 4) HALO_GRAM2(2, 4);
-                else HALO_GRAM2(2, 2);
+// The Gram route's two kernels: the 5 inner-product maps over the low-res grid, then the radius / norm of every output pixel from them.
+static void launch_gram(const halo_score_args &a, const ScorePlan &p, hipStream_t st)
+{
+    const double *feat = (const double *)a.feat;
+    const long long bstride = a.feat_bstride;
+    const int B = (int)a.B, C = (int)a.C, H = (int)a.H, W = (int)a.W, hf = (int)a.hf, wf = (int)a.wf;
+    const dim3 block(TPB);
+    // 16 bytes per lane where the planes allow it (even width, 16-byte aligned); otherwise the 8-byte kernel
+    const bool wide = wf >= 2 && wf % 2 == 0 && bstride % 2 == 0 && aligned16(feat) && aligned16(p.gram);
+    if (wide) {
+        // rows per wave: every source row is loaded (R + 1) / R times (its own strip + as lower neighbour of the strip above),
+        // and that redundancy, not the bytes in flight, is what the kernel's time follows (profiles/archive/r04_gram_ab.txt: R = 2 / 4 /
+        // 8 -> 788 / 745 / 705 us per 16 images; 2, 3 or 4 channels in flight: equal; non-temporal loads: 20 % slower).  The
+        // widest strip that still gives every SIMD of the chip a wave; one channel in flight for 8-row strips, two otherwise
+        const long long nwx = cdiv(wf, 128);
+        int rows = 2;
+        for (int cand = 8; cand > 2; cand >>= 1)
+            if (B * nwx * cdiv(hf, cand) >= 1024) { rows = cand; break; }
+        const long long nwaves = nwx * cdiv(hf, rows);
+        const dim3 gg((unsigned)(cdiv(cdiv(nwaves, TPB / 64), 8) * 8), (unsigned)B);
+#define HALO_GRAM2(U_, R_) hipLaunchKernelGGL((k_gram_lr2<U_, R_>), gg, block, 0, st, feat, bstride, C, hf, wf, p.gram)
+        if (rows == 8) HALO_GRAM2(1, 8);
+        else if (rows == 4) HALO_GRAM2(2, 4);
+        else HALO_GRAM2(2, 2);
 #undef HALO_GRAM2
-            } else {
-                const long long nwaves = cdiv(lr->wf, GRAM_COLS) * cdiv(lr->hf, 2);
-                hipLaunchKernelGGL(k_gram_lr, dim3((unsigned)(cdiv(cdiv(nwaves, TPB / 64), 8) * 8), (unsigned)B), block, 0, st, (const double *)feat,
-                                   (long long)feat_bstride, (int)C, lr->hf, lr->wf, gram);
-            }
-            if (ev_feat_mid) (void)hipEventRecord((hipEvent_t)ev_feat_mid, st);       // between the Gram pass and the radius pass
-            const double shd = H > 1 ? (double)(lr->hf - 1) / (double)(H - 1) : 0.0, swd = W > 1 ? (double)(lr->wf - 1) / (double)(W - 1) : 0.0;
-            nblk_imp = nblk1;
-            if (mode == 0) hipLaunchKernelGGL(k_radius_gram<0>, dim3((unsigned)nblk1, (unsigned)B), block, 0, st, gram, (const double *)feat, (long long)feat_bstride, (int)C, lr->hf, lr->wf, (int)H, (int)W, shd, swd, ks, rks, imp_raw, part_imp);
-            else hipLaunchKernelGGL(k_radius_gram<1>, dim3((unsigned)nblk1, (unsigned)B), block, 0, st, gram, (const double *)feat, (long long)feat_bstride, (int)C, lr->hf, lr->wf, (int)H, (int)W, shd, swd, ks, rks, imp_raw, part_imp);
-        } else if (lr) {
-            const int rc = feat_dtype == HALO_F64
-                ? launch_feat_lr<double>((const double *)feat, feat_bstride, (int)C, *lr, (int)H, (int)W, (int)B, mode, ks, rks, imp_raw, part_imp, nblk_imp, st)
-                : launch_feat_lr<float>((const float *)feat, feat_bstride, (int)C, *lr, (int)H, (int)W, (int)B, mode, ks, rks, (float *)imp_raw, part_imp, nblk_imp, st);
-            if (rc != HALO_OK) return rc;
-        } else if (feat_dtype == HALO_F64) {
-            const bool v2 = (hw % 2 == 0) && (feat_bstride % 2 == 0) && aligned16(feat) && aligned16(imp_raw);
-            if (v2) { nblk_imp = (int)cdiv(hw, FTPB * 2); launch_feat<double, 2>((const double *)feat, feat_bstride, (int)C, hw, (int)B, mode, ks, rks, imp_raw, part_imp, nblk_imp, st, flp); }
-            else { nblk_imp = (int)cdiv(hw, FTPB); launch_feat<double, 1>((const double *)feat, feat_bstride, (int)C, hw, (int)B, mode, ks, rks, imp_raw, part_imp, nblk_imp, st); }
-        } else {
-            const bool v4 = (hw % 4 == 0) && (feat_bstride % 4 == 0) && aligned16(feat) && aligned16(imp_raw);
-            if (v4) { nblk_imp = (int)cdiv(hw, FTPB * 4); launch_feat<float, 4>((const float *)feat, feat_bstride, (int)C, hw, (int)B, mode, ks, rks, (float *)imp_raw, part_imp, nblk_imp, st, flp); }
-            else { nblk_imp = (int)cdiv(hw, FTPB); launch_feat<float, 1>((const float *)feat, feat_bstride, (int)C, hw, (int)B, mode, ks, rks, (float *)imp_raw, part_imp, nblk_imp, st); }
-        }
-        if (ev_feat_stop) (void)hipEventRecord((hipEvent_t)ev_feat_stop, st);
+    } else {
+        const long long nwaves = cdiv(wf, GRAM_COLS) * cdiv(hf, 2);
+        hipLaunchKernelGGL(k_gram_lr, dim3((unsigned)(cdiv(cdiv(nwaves, TPB / 64), 8) * 8), (unsigned)B), block, 0, st, feat, bstride, C, hf, wf, p.gram);
     }
-    // everything behind the passes over the inputs may run on another stream of the caller (halo_score_maps_split): the small
-    // kernels of the tail then overlap the NEXT call's feature pass instead of standing between two of them
-    if (tail_stream && (hipStream_t)tail_stream != st) {
-        if (!need_feat || !ev_feat_stop) return fail(HALO_E_ARG, "halo_score_maps_split: a purity type that reads decoder_out and ev_feat_stop are required with a tail stream");
-        if (hipStreamWaitEvent((hipStream_t)tail_stream, (hipEvent_t)ev_feat_stop, 0) != hipSuccess)
-            return fail(HALO_E_LAUNCH, "halo_score_maps_split: hipStreamWaitEvent: %s", hipGetErrorString(hipGetLastError()));
-        st = (hipStream_t)tail_stream;
+    record(a.ev_feat_mid, st);       // between the Gram pass and the radius pass
+    const double shd = H > 1 ? (double)(hf - 1) / (double)(H - 1) : 0.0, swd = W > 1 ? (double)(wf - 1) / (double)(W - 1) : 0.0;
+    const dim3 grid1((unsigned)p.nblk1, (unsigned)B);
+    if (p.mode == 0) hipLaunchKernelGGL(k_radius_gram<0>, grid1, block, 0, st, p.gram, feat, bstride, C, hf, wf, H, W, shd, swd, p.ks, p.rks, p.imp_raw, p.part_imp);
+    else hipLaunchKernelGGL(k_radius_gram<1>, grid1, block, 0, st, p.gram, feat, bstride, C, hf, wf, H, W, shd, swd, p.ks, p.rks, p.imp_raw, p.part_imp);
+}
+
+// ---- features -> radius / norm in imp_raw (+ min / max partials, p.nblk_imp of them per image)
+static int launch_feature_pass(const halo_score_args &a, ScorePlan &p, hipStream_t st)
+{
+    const int B = (int)a.B, C = (int)a.C;
+    const long long hw = p.hw, bstride = a.feat_bstride;
+    if (p.gram) {
+        launch_gram(a, p, st);
+        p.nblk_imp = p.nblk1;
+    } else if (p.lr) {
+        return a.feat_dtype == HALO_F64 ? launch_feat_lr<double>(a, p, p.imp_raw, st)
+                                        : launch_feat_lr<float>(a, p, (float *)p.imp_raw, st);
+    } else if (a.feat_dtype == HALO_F64) {
+        const bool v2 = (hw % 2 == 0) && (bstride % 2 == 0) && aligned16(a.feat) && aligned16(p.imp_raw);
+        p.nblk_imp = (int)cdiv(hw, v2 ? FTPB * 2 : FTPB);
+        if (v2) launch_feat<double, 2>((const double *)a.feat, bstride, C, hw, B, p.mode, p.ks, p.rks, p.imp_raw, p.part_imp, p.nblk_imp, st, p.fuse ? &p.fl : nullptr);
+        else launch_feat<double, 1>((const double *)a.feat, bstride, C, hw, B, p.mode, p.ks, p.rks, p.imp_raw, p.part_imp, p.nblk_imp, st, nullptr);
+    } else {
+        const bool v4 = (hw % 4 == 0) && (bstride % 4 == 0) && aligned16(a.feat) && aligned16(p.imp_raw);
+        p.nblk_imp = (int)cdiv(hw, v4 ? FTPB * 4 : FTPB);
+        if (v4) launch_feat<float, 4>((const float *)a.feat, bstride, C, hw, B, p.mode, p.ks, p.rks, (float *)p.imp_raw, p.part_imp, p.nblk_imp, st, p.fuse ? &p.fl : nullptr);
+        else launch_feat<float, 1>((const float *)a.feat, bstride, C, hw, B, p.mode, p.ks, p.rks, (float *)p.imp_raw, p.part_imp, p.nblk_imp, st, nullptr);
     }
-    dim3 grid1((unsigned)nblk1, (unsigned)B);
-    if (pur_type == HALO_PUR_HYPER) {
-        hipLaunchKernelGGL(k_minmax_finalize, dim3((unsigned)B), block, 0, st, part_imp, nblk_imp, stats, 0);
-        if (feat_dtype == HALO_F64) hipLaunchKernelGGL((k_quantize<double, short>), grid1, block, 0, st, (const double *)imp_raw, stats, hw, (int)K, pred);
-        else hipLaunchKernelGGL((k_quantize<float, short>), grid1, block, 0, st, (const float *)imp_raw, stats, hw, (int)K, pred);
+    return HALO_OK;
+}
+
+// ---- everything behind the passes over the inputs: impurity from the bins, box sum of the uncertainty, min / max, normalise + product
+static int launch_tail(const halo_score_args &a, ScorePlan &p, hipStream_t st)
+{
+    const int64_t B = a.B, H = a.H, W = a.W;
+    const long long hw = p.hw;
+    const int normalize = p.normalize, box_pk = p.hist ? a.pksize : 0;
+    const dim3 block(TPB), grid1((unsigned)p.nblk1, (unsigned)B);
+    if (a.pur_type == HALO_PUR_HYPER) {
+        hipLaunchKernelGGL(k_minmax_finalize, dim3((unsigned)B), block, 0, st, p.part_imp, p.nblk_imp, p.stats, 0);
+        if (a.feat_dtype == HALO_F64) hipLaunchKernelGGL((k_quantize<double, short>), grid1, block, 0, st, (const double *)p.imp_raw, p.stats, hw, (int)a.K, p.pred);
+        else hipLaunchKernelGGL((k_quantize<float, short>), grid1, block, 0, st, (const float *)p.imp_raw, p.stats, hw, (int)a.K, p.pred);
     }
     // the impurity's min / max are only needed by normalize_map: per-block partials straight from the 3x3 histogram kernel,
     // a separate pass for the other sources of the map, nothing at all when the branch does not normalise (ripu.yaml)
-    if (hist) {
-        const float logK = (float)log((double)(pur_type == HALO_PUR_HYPER ? K : O));
-        const int np = launch_region_impurity<short>((const short *)pred, B, H, W, pksize, logK, (float *)imp_raw, (float *)nullptr, st,
-                                                     normalize ? part_imp : nullptr, pad);
-        nblk_imp = np ? np : nblk1;
-        if (normalize && !np) hipLaunchKernelGGL(k_minmax_f32, grid1, block, 0, st, (const float *)imp_raw, hw, part_imp);
-    } else if (pur_type == HALO_PUR_NONE) {
-        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)cdiv(B * hw, TPB)), block, 0, st, (float *)imp_raw, (long long)(B * hw), 0.0f);
-        if (normalize) hipLaunchKernelGGL(k_minmax_f32, grid1, block, 0, st, (const float *)imp_raw, hw, part_imp);
-        nblk_imp = nblk1;
+    if (p.hist) {
+        const float logK = (float)log((double)(a.pur_type == HALO_PUR_HYPER ? a.K : a.O));
+        const int np = launch_region_impurity<short>((const short *)p.pred, B, H, W, a.pksize, logK, (float *)p.imp_raw, (float *)nullptr, st,
+                                                     normalize ? p.part_imp : nullptr, p.pad);
+        p.nblk_imp = np ? np : p.nblk1;
+        if (normalize && !np) hipLaunchKernelGGL(k_minmax_f32, grid1, block, 0, st, (const float *)p.imp_raw, hw, p.part_imp);
+    } else if (a.pur_type == HALO_PUR_NONE) {
+        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)cdiv(B * hw, TPB)), block, 0, st, (float *)p.imp_raw, (long long)(B * hw), 0.0f);
+        if (normalize) hipLaunchKernelGGL(k_minmax_f32, grid1, block, 0, st, (const float *)p.imp_raw, hw, p.part_imp);
+        p.nblk_imp = p.nblk1;
     }
 
     // ---- box-sum of the uncertainty, / count
-    const int do_box = (unc_type == HALO_UNC_ENTROPY || unc_type == HALO_UNC_ORACLE_ACC) ? 1 : 0;
-    int nblk_unc = nblk1;
-    const bool box3 = do_box && pad == HALO_PAD_ZEROS && ksize == 3 && W % 4 == 0 && aligned16(ent) && aligned16(unc_raw);   // (the 3x3 fast paths pad with zeros)
+    const int do_box = (a.unc_type == HALO_UNC_ENTROPY || a.unc_type == HALO_UNC_ORACLE_ACC) ? 1 : 0;
+    const bool box3 = do_box && p.pad == HALO_PAD_ZEROS && a.ksize == 3 && W % 4 == 0 && aligned16(p.ent) && aligned16(p.unc_raw);   // (the 3x3 fast paths pad with zeros)
     // 3 x 3 window + 16-byte aligned maps: the box sum is recomputed inside the combine kernel (no stored copy); otherwise the
     // round-2 sequence (k_box3_unc / k_box_unc + k_combine, identical results)
-    const bool fuse_tail = box3 && B <= 65535 && H <= 65535 && aligned16(imp_raw) && aligned16(score) && (!impurity || aligned16(impurity)) &&
-                           (!uncertainty || aligned16(uncertainty)) && (!active || ((uintptr_t)active & 3) == 0);
-    const int nblk_c3 = (int)cdiv(hw, TPB * 4);
-    // the selector's coarse histogram of a normalised score map, counted by the combine kernel while it writes the map and handed
-    // over behind the range records (otherwise the selector counts it itself -- same picks)
-    unsigned *rng_hist = (score_range && normalize && fuse_tail)
-                             ? (unsigned *)((char *)score_range + range_hist_offset(B)) : nullptr;
+    const bool fuse_tail = box3 && B <= 65535 && H <= 65535 && aligned16(p.imp_raw) && aligned16(a.score) && (!a.impurity || aligned16(a.impurity)) &&
+                           (!a.uncertainty || aligned16(a.uncertainty)) && (!a.active || ((uintptr_t)a.active & 3) == 0);
+    // the score's value range for the selector: free when the maps are normalised and the fused combine kernel runs (the
+    // product of two values in [0, 1]); otherwise the exact reduction, here instead of in the selector.  The selector's coarse
+    // histogram of such a map is counted by the combine kernel while it writes the map and handed over behind the range
+    // records (otherwise the selector counts it itself -- same picks)
+    SelHdr *rng_free = (a.score_range && normalize && fuse_tail) ? (SelHdr *)a.score_range : nullptr;
+    unsigned *rng_hist = rng_free ? (unsigned *)((char *)a.score_range + range_hist_offset(B)) : nullptr;
     if (fuse_tail) {
         if (normalize) {            // only the min / max are needed before the combine kernel
             const dim3 gridm((unsigned)cdiv(W, BM_TW), (unsigned)cdiv(H, BM_TH), (unsigned)B);
-            nblk_unc = (int)(gridm.x * gridm.y);
-            hipLaunchKernelGGL(k_box3_minmax, gridm, block, 0, st, (const float *)ent, (int)H, (int)W, hist ? pksize : 0, part_unc, rng_hist);
+            p.nblk_unc = (int)(gridm.x * gridm.y);
+            hipLaunchKernelGGL(k_box3_minmax, gridm, block, 0, st, (const float *)p.ent, (int)H, (int)W, box_pk, p.part_unc, rng_hist);
         }
     } else if (box3) {
-        nblk_unc = nblk_c3;
-        hipLaunchKernelGGL(k_box3_unc, dim3((unsigned)nblk_unc, (unsigned)B), block, 0, st, (const float *)ent, (int)H, (int)W,
-                           hist ? pksize : 0, unc_raw, normalize ? part_unc : nullptr);
+        p.nblk_unc = (int)cdiv(hw, TPB * 4);
+        hipLaunchKernelGGL(k_box3_unc, dim3((unsigned)p.nblk_unc, (unsigned)B), block, 0, st, (const float *)p.ent, (int)H, (int)W, box_pk, p.unc_raw,
+                           normalize ? p.part_unc : nullptr);
     } else {
-        hipLaunchKernelGGL(k_box_unc, grid1, block, 0, st, ent, (int)H, (int)W, ksize, do_box, hist ? pksize : 0, unc_raw,
-                           normalize ? part_unc : nullptr, pad);
+        hipLaunchKernelGGL(k_box_unc, grid1, block, 0, st, p.ent, (int)H, (int)W, a.ksize, do_box, box_pk, p.unc_raw, normalize ? p.part_unc : nullptr, p.pad);
     }
 
     // ---- global min/max (normalize_map only), then normalise + product
-    // the score's value range for the selector: free when the maps are normalised and the fused combine kernel runs (the
-    // product of two values in [0, 1]); otherwise the exact reduction, here instead of in the selector
-    SelHdr *rng_free = (score_range && normalize && fuse_tail) ? (SelHdr *)score_range : nullptr;
     if (normalize)
-        hipLaunchKernelGGL(k_minmax_finalize2, dim3((unsigned)B, 2u), dim3(FIN_TPB), 0, st, (const double *)part_imp, nblk_imp,
-                           (const double *)part_unc, nblk_unc, stats);
+        hipLaunchKernelGGL(k_minmax_finalize2, dim3((unsigned)B, 2u), dim3(FIN_TPB), 0, st, (const double *)p.part_imp, p.nblk_imp,
+                           (const double *)p.part_unc, p.nblk_unc, p.stats);
     if (fuse_tail) {
         int crows = CB_ROWS;                 // rows per workgroup: as many as leave >= 1024 workgroups in the launch
         while (crows > 1 && cdiv(W, TPB * 4) * cdiv(H, crows) * B < 1024) crows >>= 1;
         dim3 gridc((unsigned)cdiv(W, TPB * 4), (unsigned)cdiv(H, crows), (unsigned)B);
-#define HALO_CB(T) hipLaunchKernelGGL((k_combine_box3<T>), gridc, block, 0, st, (const T *)imp_raw, (const float *)ent, stats, active, (int)H, (int)W, hist ? pksize : 0, normalize, (T *)score, (T *)impurity, uncertainty, rng_free, rng_hist, crows)
-        if (f64out) HALO_CB(double);
+#define HALO_CB(T) hipLaunchKernelGGL((k_combine_box3<T>), gridc, block, 0, st, (const T *)p.imp_raw, (const float *)p.ent, p.stats, a.active, (int)H, (int)W, box_pk, normalize, (T *)a.score, (T *)a.impurity, a.uncertainty, rng_free, rng_hist, crows)
+        if (p.f64out) HALO_CB(double);
         else HALO_CB(float);
 #undef HALO_CB
-    } else if (f64out) hipLaunchKernelGGL((k_combine<double>), grid1, block, 0, st, (const double *)imp_raw, unc_raw, stats, active, hw, normalize, (double *)score, (double *)impurity, uncertainty);
-    else hipLaunchKernelGGL((k_combine<float>), grid1, block, 0, st, (const float *)imp_raw, unc_raw, stats, active, hw, normalize, (float *)score, (float *)impurity, uncertainty);
-    if (score_range && !rng_free) {
-        const int rc = score_range_exact(score, f64out ? HALO_F64 : HALO_F32, B, hw, score_range, st);
+    } else if (p.f64out) hipLaunchKernelGGL((k_combine<double>), grid1, block, 0, st, (const double *)p.imp_raw, p.unc_raw, p.stats, a.active, hw, normalize, (double *)a.score, (double *)a.impurity, a.uncertainty);
+    else hipLaunchKernelGGL((k_combine<float>), grid1, block, 0, st, (const float *)p.imp_raw, p.unc_raw, p.stats, a.active, hw, normalize, (float *)a.score, (float *)a.impurity, a.uncertainty);
+    if (a.score_range && !rng_free) {
+        const int rc = score_range_exact(a.score, p.f64out ? HALO_F64 : HALO_F32, B, hw, a.score_range, st);
         if (rc != HALO_OK) return rc;
     }
-    if (ev_tail_stop) (void)hipEventRecord((hipEvent_t)ev_tail_stop, st);
-    return check_launch("halo_score_maps");
+    record(a.ev_tail_stop, st);
+    return check_launch("halo_score");
+}
+
+static int score_impl(const halo_score_args &a, hipStream_t st)
+{
+    ScorePlan p;
+    int rc = check_score_args(a);
+    if (rc == HALO_OK) rc = make_score_plan(a, p);
+    if (rc != HALO_OK) return rc;
+
+    record(a.ev_logit_start, st);
+    launch_logit_pass(a, p, st);
+    record(a.ev_logit_stop, st);
+    if (p.need_feat) {
+        record(a.ev_feat_start, st);
+        rc = launch_feature_pass(a, p, st);
+        if (rc != HALO_OK) return rc;
+        record(a.ev_feat_stop, st);
+    }
+    // everything behind the passes over the inputs may run on another stream of the caller: the small kernels of the tail then
+    // overlap the NEXT call's feature pass instead of standing between two of them
+    if (a.tail_stream && (hipStream_t)a.tail_stream != st) {
+        if (!p.need_feat || !a.ev_feat_stop) return fail(HALO_E_ARG, "halo_score: a purity type that reads decoder_out and ev_feat_stop are required with a tail stream");
+        if (hipStreamWaitEvent((hipStream_t)a.tail_stream, (hipEvent_t)a.ev_feat_stop, 0) != hipSuccess)
+            return fail(HALO_E_LAUNCH, "halo_score: hipStreamWaitEvent: %s", hipGetErrorString(hipGetLastError()));
+        st = (hipStream_t)a.tail_stream;
+    }
+    return launch_tail(a, p, st);
+}
+
+// FloatingRegionScore.forward for B images, from full-resolution sources or from bilinearly upsampled (align_corners=True)
+// low-resolution ones without materialising them (core/active/build.py:122-146): include/halo_hip.h describes the descriptor.
+extern "C" int halo_score(const halo_score_args *a, void *stream)
+{
+    if (!a) return fail(HALO_E_ARG, "halo_score: null descriptor");
+    return score_impl(*a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- helper-method entry points
@@ -2572,98 +2639,13 @@ extern "C" int halo_quantize_radius(const void *feat, int feat_dtype, int64_t fe
     const double ks = sqrt(fabs(-c) + 1e-15), rks = 1.0 / ks;
     dim3 block(TPB), grid1((unsigned)nblk1, (unsigned)B);
     if (feat_dtype == HALO_F64) {
-        launch_feat<double, 1>((const double *)feat, feat_bstride, (int)C, hw, (int)B, 0, ks, rks, imp_raw, part, nblkf, st);
+        launch_feat<double, 1>((const double *)feat, feat_bstride, (int)C, hw, (int)B, 0, ks, rks, imp_raw, part, nblkf, st, nullptr);
         hipLaunchKernelGGL(k_minmax_finalize, dim3((unsigned)B), block, 0, st, (const double *)part, nblkf, stats, 0);
         hipLaunchKernelGGL((k_quantize<double, long long>), grid1, block, 0, st, (const double *)imp_raw, (const double *)stats, hw, (int)K, (long long *)pred);
     } else {
-        launch_feat<float, 1>((const float *)feat, feat_bstride, (int)C, hw, (int)B, 0, ks, rks, (float *)imp_raw, part, nblkf, st);
+        launch_feat<float, 1>((const float *)feat, feat_bstride, (int)C, hw, (int)B, 0, ks, rks, (float *)imp_raw, part, nblkf, st, nullptr);
         hipLaunchKernelGGL(k_minmax_finalize, dim3((unsigned)B), block, 0, st, (const double *)part, nblkf, stats, 0);
         hipLaunchKernelGGL((k_quantize<float, long long>), grid1, block, 0, st, (const float *)imp_raw, (const double *)stats, hw, (int)K, (long long *)pred);
     }
     return check_launch("halo_quantize_radius");
-}
-
-extern "C" int halo_score_maps_timed(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                                     int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                                     int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                                     int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                                     void *workspace, size_t workspace_bytes, void *stream, void *ev_feat_start,
-                                     void *ev_feat_stop, void *score_range)
-{
-    return score_impl(logit, logit_bstride, feat, feat_dtype, feat_bstride, gt, active, B, O, C, H, W, unc_type, pur_type,
-                      normalize, ksize, pksize, K, c, score, impurity, uncertainty, workspace, workspace_bytes, stream,
-                      ev_feat_start, ev_feat_stop, nullptr, nullptr, nullptr, score_range);
-}
-
-// halo_score_maps_timed with the tail (min / max, normalisation, product, mask: everything behind the passes over logit and
-// decoder_out) enqueued on `tail_stream`, which first waits for ev_feat_stop (recorded on `stream` behind the feature pass).
-// The outputs are complete on tail_stream; the workspace belongs to the call until then.
-extern "C" int halo_score_maps_split(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                                     int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                                     int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                                     int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                                     void *workspace, size_t workspace_bytes, void *stream, void *tail_stream, void *ev_feat_start,
-                                     void *ev_feat_stop, void *score_range)
-{
-    return score_impl(logit, logit_bstride, feat, feat_dtype, feat_bstride, gt, active, B, O, C, H, W, unc_type, pur_type,
-                      normalize, ksize, pksize, K, c, score, impurity, uncertainty, workspace, workspace_bytes, stream,
-                      ev_feat_start, ev_feat_stop, nullptr, nullptr, nullptr, score_range, tail_stream);
-}
-
-// FloatingRegionScore.forward on bilinearly upsampled (align_corners=True) low-resolution sources
-// without materialising them: logit_lr (B,O,hl,wl) f32, feat_lr (B,C,hf,wf) f64|f32 -> maps (B,H,W).
-// = core/active/build.py:122-144 for B images (resize of output and decoder_out + the scorer).
-extern "C" int halo_score_maps_lr(const float *logit_lr, int64_t logit_bstride, int64_t hl, int64_t wl, const void *feat_lr,
-                                  int feat_dtype, int64_t feat_bstride, int64_t hf, int64_t wf, const int64_t *gt,
-                                  const uint8_t *active, int64_t B, int64_t O, int64_t C, int64_t H, int64_t W, int unc_type,
-                                  int pur_type, int normalize, int ksize, int pksize, int64_t K, double c, void *score,
-                                  void *impurity, float *uncertainty, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (hl <= 0 || wl <= 0) return fail(HALO_E_ARG, "halo_score_maps_lr: bad low-res logit size");
-    const bool need_feat = pur_type == HALO_PUR_HYPER || pur_type == HALO_PUR_RADIUS || pur_type == HALO_PUR_EUC_NORM;
-    if (need_feat && (hf <= 0 || wf <= 0)) return fail(HALO_E_ARG, "halo_score_maps_lr: bad low-res embedding size");
-    LrDims lr{(int)hl, (int)wl, (int)hf, (int)wf, false};
-    return score_impl(logit_lr, logit_bstride, feat_lr, feat_dtype, feat_bstride, gt, active, B, O, C, H, W, unc_type, pur_type,
-                      normalize, ksize, pksize, K, c, score, impurity, uncertainty, workspace, workspace_bytes, stream, nullptr,
-                      nullptr, &lr);
-}
-
-extern "C" int halo_score_maps_lr_gram(const float *logit_lr, int64_t logit_bstride, int64_t hl, int64_t wl, const void *feat_lr,
-                                       int feat_dtype, int64_t feat_bstride, int64_t hf, int64_t wf, const int64_t *gt,
-                                       const uint8_t *active, int64_t B, int64_t O, int64_t C, int64_t H, int64_t W, int unc_type,
-                                       int pur_type, int normalize, int ksize, int pksize, int64_t K, double c, void *score,
-                                       void *impurity, float *uncertainty, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (hl <= 0 || wl <= 0) return fail(HALO_E_ARG, "halo_score_maps_lr_gram: bad low-res logit size");
-    const bool need_feat = pur_type == HALO_PUR_HYPER || pur_type == HALO_PUR_RADIUS || pur_type == HALO_PUR_EUC_NORM;
-    if (need_feat && (hf <= 0 || wf <= 0)) return fail(HALO_E_ARG, "halo_score_maps_lr_gram: bad low-res embedding size");
-    if (need_feat && hf * wf > 0x7fffffffll) return fail(HALO_E_UNSUPPORTED, "halo_score_maps_lr_gram: low-res planes of more than 2^31 elements");
-    if (need_feat && workspace_bytes < halo_score_lr_gram_workspace_bytes(B, O, H, W, hf, wf))
-        return fail(HALO_E_WORKSPACE, "halo_score_maps_lr_gram: workspace too small");
-    LrDims lr{(int)hl, (int)wl, (int)hf, (int)wf, true};
-    return score_impl(logit_lr, logit_bstride, feat_lr, feat_dtype, feat_bstride, gt, active, B, O, C, H, W, unc_type, pur_type,
-                      normalize, ksize, pksize, K, c, score, impurity, uncertainty, workspace, workspace_bytes, stream, nullptr,
-                      nullptr, &lr);
-}
-
-// halo_score_maps_lr (gram = 0) / halo_score_maps_lr_gram (gram = 1) with optional hipEvent_t handles (halo_event_create) recorded on
-// `stream` around the logit pass (k_logit_maps_lr), around the embedding pass (k_feat_reduce_lr, or k_gram_lr + k_radius_gram, with
-// ev_feat_mid between the two) and behind the tail (ev_tail_stop) -- bench.py's live per-kernel times for the low-resolution boundary.
-extern "C" int halo_score_maps_lr_timed(const float *logit_lr, int64_t logit_bstride, int64_t hl, int64_t wl, const void *feat_lr,
-                                        int feat_dtype, int64_t feat_bstride, int64_t hf, int64_t wf, const int64_t *gt,
-                                        const uint8_t *active, int64_t B, int64_t O, int64_t C, int64_t H, int64_t W, int unc_type,
-                                        int pur_type, int normalize, int ksize, int pksize, int64_t K, double c, void *score,
-                                        void *impurity, float *uncertainty, void *workspace, size_t workspace_bytes, void *stream,
-                                        int gram, void *ev_logit_start, void *ev_logit_stop, void *ev_feat_start, void *ev_feat_stop,
-                                        void *score_range, void *ev_feat_mid, void *ev_tail_stop)
-{
-    if (hl <= 0 || wl <= 0) return fail(HALO_E_ARG, "halo_score_maps_lr_timed: bad low-res logit size");
-    const bool need_feat = pur_type == HALO_PUR_HYPER || pur_type == HALO_PUR_RADIUS || pur_type == HALO_PUR_EUC_NORM;
-    if (need_feat && (hf <= 0 || wf <= 0)) return fail(HALO_E_ARG, "halo_score_maps_lr_timed: bad low-res embedding size");
-    if (gram && need_feat && workspace_bytes < halo_score_lr_gram_workspace_bytes(B, O, H, W, hf, wf))
-        return fail(HALO_E_WORKSPACE, "halo_score_maps_lr_timed: workspace too small");
-    LrDims lr{(int)hl, (int)wl, (int)hf, (int)wf, gram != 0};
-    return score_impl(logit_lr, logit_bstride, feat_lr, feat_dtype, feat_bstride, gt, active, B, O, C, H, W, unc_type, pur_type,
-                      normalize, ksize, pksize, K, c, score, impurity, uncertainty, workspace, workspace_bytes, stream, ev_feat_start,
-                      ev_feat_stop, &lr, ev_logit_start, ev_logit_stop, score_range, nullptr, ev_feat_mid, ev_tail_stop);
 }

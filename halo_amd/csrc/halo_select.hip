@@ -308,15 +308,6 @@ static int launch_resume(const SelGeom &g, size_t lds, dim3 grid, hipStream_t st
     return HALO_OK;
 }
 
-extern "C" int halo_greedy_select(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
-                                  int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
-                                  int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
-                                  void *workspace, size_t workspace_bytes, int method, void *stream)
-{
-    return halo_greedy_select_ranged(score, dtype, B, H, W, n_regions, active_radius, mask_radius, active, selected, active_mask, gt,
-                                     picks, n_picked, workspace, workspace_bytes, method, nullptr, stream);
-}
-
 extern "C" size_t halo_score_range_bytes(int64_t B) { return B > 0 ? range_hist_offset(B) + (size_t)B * NB1 * sizeof(unsigned) : 0; }
 
 extern "C" int halo_score_range(const void *score, int dtype, int64_t B, int64_t H, int64_t W, void *score_range, void *stream)
@@ -325,15 +316,6 @@ extern "C" int halo_score_range(const void *score, int dtype, int64_t B, int64_t
     if (dtype != HALO_F32 && dtype != HALO_F64) return fail(HALO_E_ARG, "halo_score_range: bad dtype");
     const int rc = score_range_exact(score, dtype, B, H * W, score_range, (hipStream_t)stream);
     return rc != HALO_OK ? rc : check_launch("halo_score_range");
-}
-
-extern "C" int halo_greedy_select_ranged(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
-                                         int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
-                                         int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
-                                         void *workspace, size_t workspace_bytes, int method, const void *score_range, void *stream)
-{
-    return halo_greedy_select_ex(score, dtype, B, H, W, n_regions, active_radius, mask_radius, active, selected, active_mask, gt, picks,
-                                 n_picked, workspace, workspace_bytes, method, score_range, nullptr, stream);
 }
 
 namespace halo {
@@ -345,11 +327,12 @@ __global__ void __launch_bounds__(256) k_sel_not_run(int *__restrict__ handover,
 }
 }  // namespace halo
 
-extern "C" int halo_greedy_select_ex(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
-                                     int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
-                                     int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
-                                     void *workspace, size_t workspace_bytes, int method, const void *score_range,
-                                     int32_t *handover, void *stream)
+// score_range (the scorer's range records) and handover (what the sweep did with each image) may be NULL: include/halo_hip.h
+extern "C" int halo_greedy_select(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
+                                  int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
+                                  int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
+                                  void *workspace, size_t workspace_bytes, int method, const void *score_range,
+                                  int32_t *handover, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
     if (!score || !active || !selected || !active_mask || !gt || B <= 0 || H <= 0 || W <= 0)

@@ -887,7 +887,7 @@ BinPlan binned_plan(int64_t B, int64_t H, int64_t W, int64_t n_regions, int64_t 
     return p;
 }
 
-// The exact value range of score maps as the record halo_greedy_select_ranged accepts (also the scorer's fallback when it
+// The exact value range of score maps as the record halo_greedy_select accepts (also the scorer's fallback when it
 // cannot bound the range for free): zero the records, then the same reduction the selector runs on its own.
 int score_range_exact(const void *score, int dtype, int64_t B, int64_t hw, void *range_out, hipStream_t st)
 {

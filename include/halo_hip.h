@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 10
+#define HALO_ABI_VERSION 11
 
 enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4 };
 
@@ -45,8 +45,8 @@ enum { HALO_UNC_ENTROPY = 0, HALO_UNC_PIXEL_ENTROPY = 1, HALO_UNC_ORACLE_ACC = 2
  * outside the image reads.  ZEROS (every caller in the reference's tree): nothing, and the purity window counts its in-image
  * taps only; REFLECT / REPLICATE / CIRCULAR: the image pixel torch's F.pad(mode) puts there, so every tap counts. */
 enum { HALO_PAD_ZEROS = 0, HALO_PAD_REFLECT = 1, HALO_PAD_REPLICATE = 2, HALO_PAD_CIRCULAR = 3 };
-/* The `normalize` argument of the halo_score_maps* calls is a flags word: bit 0 = normalise both maps (the reference's
- * `normalize`), bits 8-9 = HALO_PAD_* << 8.  Passing 0 / 1 keeps its old meaning (zero padding). */
+/* halo_score_args.flags: bit 0 = normalise both maps (the reference's `normalize`), bits 8-9 = HALO_PAD_* << 8.  0 / 1 mean
+ * zero padding. */
 enum { HALO_FLAG_NORMALIZE = 1 };
 #define HALO_FLAG_PAD(mode) ((mode) << 8)
 
@@ -131,88 +131,104 @@ int halo_bilinear_upsample_bwd(const void *grad_out, void *grad_in, int dtype, i
 
 /* ---- scoring: FloatingRegionScore.forward (core/active/floating_region.py:129-217) ----
  *
- * logit (B,O,H,W) f32; feat = decoder_out (B,C,H,W) f64|f32, needed for pur HYPER/RADIUS/EUC_NORM
- * (may be NULL otherwise); gt (B,H,W) i64, needed for UNC_ORACLE_ACC / PUR_ORACLE_RIPU.
- * ksize  = entropy_conv size (constructor `size`);  pksize = purity_conv size (3 if the module
- * was built with purity_type=='hyper', floating_region.py:54-55);  K = histogram bins for HYPER.
- * Outputs (B,H,W): score and impurity are f64 when pur is RADIUS|EUC_NORM and feat is f64,
- * otherwise f32 (the reference's type promotion, floating_region.py:210); uncertainty is f32.
- * impurity / uncertainty may be NULL when only the score is wanted.
- * active (B,H,W) u8, optional: where non-zero the score is written as -inf, fusing
- * `score[active] = -inf` (core/active/build.py:146); pass NULL for the plain forward.
+ * ONE call, halo_score(&args, stream), described by a halo_score_args.  The descriptor is plain data that is read only
+ * during the call (build it on the stack; nothing keeps a pointer to it, so a captured graph does not depend on it either).
+ * (ABI 11 collapsed six positional entry points and two of their three workspace queries into this one; no kernel changed.)
+ *
+ * route: where the two sources live.
+ *   HALO_SCORE_FULL     logit (B,O,H,W) f32 and feat = decoder_out (B,C,H,W) at the maps' resolution; hl, wl, hf, wf are ignored.
+ *   HALO_SCORE_LR       LOW-RESOLUTION sources, fusing RegionSelection's two F.interpolate calls (core/active/build.py:122-135)
+ *                       into the scorer: logit (B,O,hl,wl) f32 and feat (B,C,hf,wf) f64|f32 are interpolated on the fly (bilinear,
+ *                       align_corners=True) to (H,W); the C x H x W tensor is never materialised.  Results are bit-identical to
+ *                       halo_bilinear_upsample + HALO_SCORE_FULL.  Returns HALO_E_UNSUPPORTED when a source window does not
+ *                       fit LDS (strong downsampling): the caller then upsamples explicitly.
+ *   HALO_SCORE_LR_GRAM  HALO_SCORE_LR with the embedding's radius / norm evaluated through the Gram form SURVEY 8f N1 describes:
+ *                       ||sum_i w_i v_i||^2 = sum_{i<=j} (2 - [i==j]) w_i w_j <v_i, v_j> over the four corner vectors of an output
+ *                       pixel's low-res cell -- the inner products are computed once (one pass over feat; 5 maps over the low-res
+ *                       grid hold them), each output pixel then costs 10 terms instead of C.  Same mathematics, different rounding
+ *                       (|difference| of the sum of squares: a few 1e-16 of the largest corner norm^2), so this route is NOT
+ *                       bit-identical to upsample + HALO_SCORE_FULL; float64 feat only (HALO_E_UNSUPPORTED otherwise).  Everything
+ *                       else (logits, normalisation, -inf masking) as HALO_SCORE_LR; a purity type that does not read feat makes
+ *                       the two routes the same.  hf * wf above 2^31 - 1 is HALO_E_UNSUPPORTED and a workspace below
+ *                       halo_score_args_workspace_bytes is HALO_E_WORKSPACE on EVERY call of this route (before ABI 11 the
+ *                       timed variant of the call skipped the first check: the one intended tightening of the collapse).
+ *   On the two low-res routes hl, wl <= 0, or hf, wf <= 0 with a purity type that reads feat, are HALO_E_ARG.
+ *
+ * sources
+ *   logit, logit_bstride   f32, image b at logit + b * logit_bstride (ELEMENTS; planes dense)
+ *   hl, wl                 size of the low-res logit planes (low-res routes)
+ *   feat, feat_dtype, feat_bstride   HALO_F64 | HALO_F32, needed for pur HYPER / RADIUS / EUC_NORM (may be NULL otherwise)
+ *   hf, wf                 size of the low-res embedding planes (low-res routes)
+ *   gt                     (B,H,W) i64, needed for UNC_ORACLE_ACC / PUR_ORACLE_RIPU
+ *   active                 (B,H,W) u8, optional: where non-zero the score is written as -inf, fusing `score[active] = -inf`
+ *                          (core/active/build.py:146); NULL for the plain forward
+ * geometry + parameters
+ *   B, O, C, H, W          images, classes, embedding channels, size of the maps
+ *   unc_type, pur_type     HALO_UNC_* / HALO_PUR_*; a pur_type outside the enum is the reference's NotImplementedError
+ *                          (HALO_E_UNSUPPORTED, "... not implemented")
+ *   flags                  bit 0 = HALO_FLAG_NORMALIZE: normalise both maps (the reference's `normalize`); bits 8-9 =
+ *                          HALO_FLAG_PAD(HALO_PAD_*): padding mode of the two box windows.  0 / 1 mean zero padding; any other
+ *                          bit is HALO_E_ARG
+ *   ksize, pksize          entropy_conv size (constructor `size`) and purity_conv size (3 if the module was built with
+ *                          purity_type=='hyper', floating_region.py:54-55); both odd
+ *   K, c                   histogram bins for HYPER; curvature
+ * outputs, (B,H,W)
+ *   score, impurity        f64 when pur is RADIUS | EUC_NORM and feat is f64, otherwise f32 (the reference's type promotion,
+ *                          floating_region.py:210)
+ *   uncertainty            f32.  impurity / uncertainty may be NULL when only the score is wanted
+ * scratch
+ *   workspace, workspace_bytes   at least halo_score_args_workspace_bytes(&args): right for every route (FULL: what
+ *                          halo_score_workspace_bytes(B, H, W) returns; the low-res routes add an upsampled logit tensor for class
+ *                          counts other than 19 / 16, the Gram route its 5 maps); 0 for a NULL descriptor, another struct_bytes, an
+ *                          empty shape or an unknown route
+ * optional, NULL = none, honoured on every route
+ *   tail_stream            a second stream of the caller: the passes over logit and feat run on `stream`, ev_feat_stop (then
+ *                          required) is recorded behind them, tail_stream waits for it and receives every launch after that (min /
+ *                          max, normalize_map, the product, score[active] = -inf: floating_region.py:204-217 + build.py:146).  The
+ *                          small tail kernels of one call then overlap the feature pass of the NEXT call on `stream` instead of
+ *                          standing between two of them.  The outputs are complete on tail_stream; `workspace` belongs to the call
+ *                          until then (one workspace per call in flight).  Needs a purity type that reads decoder_out.
+ *                          tail_stream == stream: the same as NULL
+ *   score_range            a buffer of halo_score_range_bytes(B) bytes for these B maps: receives the value range of each score map
+ *                          -- and, for normalised maps, the selector's coarse histogram of it -- in the form halo_greedy_select
+ *                          accepts, so that the selector need not read the map once or twice more to find them.  Free when the
+ *                          maps are normalised (a product of two values in [0, 1]); otherwise the range is reduced exactly and no
+ *                          histogram is handed over
+ *   ev_*                   hipEvent_t (as void*, from halo_event_create) recorded on `stream`: ev_logit_start / ev_logit_stop around
+ *                          the logit pass, ev_feat_start / ev_feat_stop immediately before and after the embedding pass (k_feat_reduce,
+ *                          the HBM-roofline kernel; only recorded when the purity type reads feat), ev_feat_mid between the Gram pass
+ *                          and the radius pass of the Gram route, ev_tail_stop behind the tail kernels (on tail_stream when there is
+ *                          one) -- bench.py times the kernels live inside the pipelined run with them
  */
-size_t halo_score_workspace_bytes(int64_t B, int64_t H, int64_t W);
-int halo_score_maps(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                    int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                    int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                    int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                    void *workspace, size_t workspace_bytes, void *stream);
-
-/* Same call with two optional hipEvent_t (as void*, from halo_event_create) recorded on `stream`
- * immediately before and after the feature-reduction kernel (k_feat_reduce, the HBM-roofline
- * kernel) -- used by bench.py to time that kernel live inside the pipelined run -- and an optional
- * `score_range` output (a buffer of halo_score_range_bytes(B) bytes for these B maps, NULL = none): the value range of each
- * score map -- and, for normalised maps, the selector's coarse histogram of it -- in the form halo_greedy_select_ranged
- * accepts, so that the selector need not read the map once or twice more to find them.  Free when the maps are normalised
- * (a product of two values in [0, 1]); otherwise the range is reduced exactly and no histogram is handed over. */
-int halo_score_maps_timed(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                          int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                          int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                          int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                          void *workspace, size_t workspace_bytes, void *stream, void *ev_feat_start,
-                          void *ev_feat_stop, void *score_range);
-
-/* halo_score_maps_timed with its tail on a second stream of the caller: the passes over `logit` and `feat` run on `stream`,
- * ev_feat_stop (required) is recorded behind them, `tail_stream` waits for it and receives every launch after that (min / max,
- * normalize_map, the product, score[active] = -inf: floating_region.py:204-217 + build.py:146).  The small tail kernels of
- * one call then overlap the feature pass of the NEXT call on `stream` instead of standing between two of them.  The outputs are
- * complete on tail_stream; `workspace` belongs to the call until then (one workspace per call in flight).  Needs a purity type
- * that reads decoder_out.  tail_stream == stream or NULL: the same as halo_score_maps_timed. */
-int halo_score_maps_split(const float *logit, int64_t logit_bstride, const void *feat, int feat_dtype,
-                          int64_t feat_bstride, const int64_t *gt, const uint8_t *active, int64_t B, int64_t O,
-                          int64_t C, int64_t H, int64_t W, int unc_type, int pur_type, int normalize, int ksize,
-                          int pksize, int64_t K, double c, void *score, void *impurity, float *uncertainty,
-                          void *workspace, size_t workspace_bytes, void *stream, void *tail_stream, void *ev_feat_start,
-                          void *ev_feat_stop, void *score_range);
-
-/* The same forward on LOW-RESOLUTION sources, fusing RegionSelection's two F.interpolate calls
- * (core/active/build.py:122-135) into the scorer: logit_lr (B,O,hl,wl) f32 and feat_lr (B,C,hf,wf)
- * f64|f32 are interpolated on the fly (bilinear, align_corners=True) to (H,W); the C x H x W tensor is
- * never materialised.  Results are bit-identical to halo_bilinear_upsample + halo_score_maps.
- * Returns HALO_E_UNSUPPORTED when a source window does not fit LDS (strong downsampling): the caller
- * then upsamples explicitly.  workspace: halo_score_lr_workspace_bytes(B, O, H, W). */
-size_t halo_score_lr_workspace_bytes(int64_t B, int64_t O, int64_t H, int64_t W);
-int halo_score_maps_lr(const float *logit_lr, int64_t logit_bstride, int64_t hl, int64_t wl, const void *feat_lr,
-                       int feat_dtype, int64_t feat_bstride, int64_t hf, int64_t wf, const int64_t *gt,
-                       const uint8_t *active, int64_t B, int64_t O, int64_t C, int64_t H, int64_t W, int unc_type,
-                       int pur_type, int normalize, int ksize, int pksize, int64_t K, double c, void *score,
-                       void *impurity, float *uncertainty, void *workspace, size_t workspace_bytes, void *stream);
-
-/* halo_score_maps_lr with the embedding's radius / norm evaluated through the Gram form SURVEY 8f N1 describes:
- * ||sum_i w_i v_i||^2 = sum_{i<=j} (2 - [i==j]) w_i w_j <v_i, v_j> over the four corner vectors of an output pixel's low-res
- * cell -- the inner products are computed once (one pass over feat_lr; 5 maps over the low-res grid hold them), each
- * output pixel then costs 10 terms instead of C.  Same mathematics, different rounding (|difference| of the sum of squares: a few 1e-16 of the
- * largest corner norm^2), so this call is NOT bit-identical to upsample + halo_score_maps; float64 feat_lr only
- * (HALO_E_UNSUPPORTED otherwise).  Everything else (logits, normalisation, -inf masking) as halo_score_maps_lr.
- * workspace: halo_score_lr_gram_workspace_bytes(B, O, H, W, hf, wf). */
-size_t halo_score_lr_gram_workspace_bytes(int64_t B, int64_t O, int64_t H, int64_t W, int64_t hf, int64_t wf);
-int halo_score_maps_lr_gram(const float *logit_lr, int64_t logit_bstride, int64_t hl, int64_t wl, const void *feat_lr,
-                            int feat_dtype, int64_t feat_bstride, int64_t hf, int64_t wf, const int64_t *gt,
-                            const uint8_t *active, int64_t B, int64_t O, int64_t C, int64_t H, int64_t W, int unc_type,
-                            int pur_type, int normalize, int ksize, int pksize, int64_t K, double c, void *score,
-                            void *impurity, float *uncertainty, void *workspace, size_t workspace_bytes, void *stream);
-
-/* Either of the two calls above (gram = 0 / 1) with optional hipEvent_t pairs (void*, from halo_event_create; NULL = none) recorded on
- * `stream` around the logit pass, around the embedding pass (ev_feat_mid: between the Gram pass and the radius pass of the
- * gram route) and behind the tail kernels (ev_tail_stop) -- bench.py times the kernels of the low-resolution boundary live
- * with them. */
-int halo_score_maps_lr_timed(const float *logit_lr, int64_t logit_bstride, int64_t hl, int64_t wl, const void *feat_lr,
-                             int feat_dtype, int64_t feat_bstride, int64_t hf, int64_t wf, const int64_t *gt,
-                             const uint8_t *active, int64_t B, int64_t O, int64_t C, int64_t H, int64_t W, int unc_type,
-                             int pur_type, int normalize, int ksize, int pksize, int64_t K, double c, void *score,
-                             void *impurity, float *uncertainty, void *workspace, size_t workspace_bytes, void *stream,
-                             int gram, void *ev_logit_start, void *ev_logit_stop, void *ev_feat_start, void *ev_feat_stop,
-                             void *score_range, void *ev_feat_mid, void *ev_tail_stop);
+enum { HALO_SCORE_FULL = 0, HALO_SCORE_LR = 1, HALO_SCORE_LR_GRAM = 2 };
+typedef struct halo_score_args {
+    size_t struct_bytes;            /* sizeof(halo_score_args) as the caller compiled it; anything else: HALO_E_ARG */
+    int route;                      /* HALO_SCORE_* */
+    const float *logit;
+    int64_t logit_bstride;
+    int64_t hl, wl;
+    const void *feat;
+    int feat_dtype;
+    int64_t feat_bstride;
+    int64_t hf, wf;
+    const int64_t *gt;
+    const uint8_t *active;
+    int64_t B, O, C, H, W;
+    int unc_type, pur_type, flags, ksize, pksize;
+    int64_t K;
+    double c;
+    void *score;
+    void *impurity;
+    float *uncertainty;
+    void *workspace;
+    size_t workspace_bytes;
+    void *tail_stream;
+    void *score_range;
+    void *ev_logit_start, *ev_logit_stop, *ev_feat_start, *ev_feat_mid, *ev_feat_stop, *ev_tail_stop;
+} halo_score_args;
+size_t halo_score_workspace_bytes(int64_t B, int64_t H, int64_t W);     /* route FULL; also halo_quantize_radius's scratch */
+size_t halo_score_args_workspace_bytes(const halo_score_args *a);
+int halo_score(const halo_score_args *a, void *stream);
 
 /* Helper methods of FloatingRegionScore that are public by convention:
  *  - compute_region_uncertainty(unc_type, logit, p, ground_truth) / compute_pixel_entropy(p)
@@ -249,41 +265,31 @@ int halo_quantize_radius(const void *feat, int feat_dtype, int64_t feat_bstride,
  * workspace: halo_select_workspace_bytes(B, H, W, n_regions, mask_radius). */
 enum { HALO_SELECT_AUTO = 0, HALO_SELECT_SERIAL = 1, HALO_SELECT_BINNED = 2 };
 size_t halo_select_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t n_regions, int64_t mask_radius);
-int halo_greedy_select(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
-                       int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
-                       int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
-                       void *workspace, size_t workspace_bytes, int method, void *stream);
-
-/* halo_greedy_select given the value range of each score map (`score_range`: a buffer of halo_score_range_bytes(B) bytes filled
- * by halo_score_maps_timed / halo_score_maps_lr_timed or halo_score_range for the same B maps; NULL = find it here).  The range
+/* `score_range`: the value range of each score map, a buffer of halo_score_range_bytes(B) bytes filled by halo_score
+ * (halo_score_args.score_range) or halo_score_range for the same B maps; NULL = find it here.  The range
  * only has to BOUND the finite values: the binning is monotone, so the picks do not depend on it.  The buffer also holds room
  * for the selector's coarse histogram of each map (2048 counters): for normalised maps the scorer counts it while it writes the
  * score and marks the record; the selector then skips its pass over the map and CLEARS the mark (the buffer is written through
  * the const pointer's storage: the counts describe the map as it was scored and are used once; should the caller have changed
  * the map in between, the sweep hands an exhausted image over to the serial kernel instead of trusting them -- results never
- * depend on the histogram).  halo_score_range computes the exact range records of existing maps (no histogram). */
-size_t halo_score_range_bytes(int64_t B);
-int halo_score_range(const void *score, int dtype, int64_t B, int64_t H, int64_t W, void *score_range, void *stream);
-int halo_greedy_select_ranged(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
-                              int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
-                              int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
-                              void *workspace, size_t workspace_bytes, int method, const void *score_range, void *stream);
-
-/* halo_greedy_select_ranged that also REPORTS what the value-binned sweep did with each image: `handover` (B,2) i32, NULL = do
- * not report; row b = {reason, picks the sweep made before it stopped}.  Reason 0 = the sweep finished the image; anything else =
- * the serial kernel continued it from that pick on (results are identical either way -- this is a cost counter: a handed-over
- * image costs milliseconds instead of tens of microseconds). */
+ * depend on the histogram).  halo_score_range computes the exact range records of existing maps (no histogram).
+ * `handover` (B,2) i32, NULL = do not report: what the value-binned sweep did with each image; row b = {reason, picks the sweep
+ * made before it stopped}.  Reason 0 = the sweep finished the image; anything else = the serial kernel continued it from that
+ * pick on (results are identical either way -- this is a cost counter: a handed-over image costs milliseconds instead of tens
+ * of microseconds). */
 enum { HALO_SWEEP_DONE = 0,
        HALO_SWEEP_BAD_VALUES = 1,     /* NaN / +inf in the map, a constant map, or nothing pickable: no value range to bin */
        HALO_SWEEP_BIN_OVERFLOW = 2,   /* a run of candidates too dense for its value bins (a plateau of ties) */
        HALO_SWEEP_SURVIVORS = 3,      /* more unsuppressed candidates in one step than the resolve stage holds */
        HALO_SWEEP_EXHAUSTED = 4,      /* candidates ran out behind a dropped threshold bin / a stale histogram */
        HALO_SWEEP_NOT_RUN = 5 };      /* serial method, or a geometry the sweep does not serve */
-int halo_greedy_select_ex(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
-                          int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
-                          int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
-                          void *workspace, size_t workspace_bytes, int method, const void *score_range,
-                          int32_t *handover, void *stream);
+size_t halo_score_range_bytes(int64_t B);
+int halo_score_range(const void *score, int dtype, int64_t B, int64_t H, int64_t W, void *score_range, void *stream);
+int halo_greedy_select(void *score, int dtype, int64_t B, int64_t H, int64_t W, int64_t n_regions,
+                       int64_t active_radius, int64_t mask_radius, uint8_t *active, uint8_t *selected,
+                       int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
+                       void *workspace, size_t workspace_bytes, int method, const void *score_range,
+                       int32_t *handover, void *stream);
 
 /* ---- pool side of the round: image-wise sharding, ONE all-gather of pick tables (the reference runs the
  * round on rank 0 only, core/train_learners.py:307-326) ----

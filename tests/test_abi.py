@@ -19,7 +19,7 @@ def _declared_symbols():
 
 def test_header_declares_expected_entry_points():
     syms = _declared_symbols()
-    for must in ("halo_expmap0_project", "halo_hypermlr_logits", "halo_dist0", "halo_pdist", "halo_score_maps",
+    for must in ("halo_expmap0_project", "halo_hypermlr_logits", "halo_dist0", "halo_pdist", "halo_score",
                  "halo_greedy_select", "halo_version", "halo_last_error", "halo_bilinear_upsample"):
         assert must in syms
 
@@ -59,6 +59,29 @@ def test_workspace_queries_are_pure_host_functions():
     L = _lib.lib()
     assert L.halo_score_workspace_bytes(1, 1024, 2048) >= 1024 * 2048 * 18
     assert L.halo_score_workspace_bytes(0, 4, 4) == 0
+    # halo_score_args_workspace_bytes: the arena of halo_score.hip written out (256-byte aligned pieces: ent and unc_raw f32, imp_raw
+    # f64, pred i16, two tables of min / max partials -- one slot per 128 pixels or per 64 x 16 tile, whichever are more -- and the
+    # stats), + 1 KiB; the low-res routes add the upsampled logits of a class count other than 19 / 16, the Gram route its 5 maps
+    def up(x):
+        return (x + 255) // 256 * 256
+    B, H, W = 1, 1024, 2048
+    n = B * H * W
+    slots = max(-(-H * W // 128), -(-W // 64) * -(-H // 16))
+    base = 2 * up(n * 4) + up(n * 8) + up(n * 2) + 2 * up(B * slots * 2 * 8) + up(B * 4 * 8) + 1024
+    assert L.halo_score_workspace_bytes(B, H, W) == base
+
+    def query(route, **kw):
+        a = _lib.ScoreArgs(struct_bytes=ctypes.sizeof(_lib.ScoreArgs), route=route, B=B, H=H, W=W, **kw)
+        return L.halo_score_args_workspace_bytes(ctypes.byref(a))
+    assert query(_lib.SCORE_FULL) == base
+    assert query(_lib.SCORE_LR, O=19) == base
+    assert query(_lib.SCORE_LR, O=7) == base + B * 7 * H * W * 4 + 512
+    assert query(_lib.SCORE_LR_GRAM, O=19, hf=160, wf=320) == base + B * 5 * 160 * 320 * 8 + 512
+    assert query(_lib.SCORE_LR_GRAM, O=7, hf=160, wf=320) == base + B * 7 * H * W * 4 + 512 + B * 5 * 160 * 320 * 8 + 512
+    # the degenerate inputs of the three queries this one replaced, an unknown route, a descriptor of another size
+    assert query(_lib.SCORE_LR, O=0) == 0 and query(_lib.SCORE_LR_GRAM, O=19, hf=0, wf=320) == 0 and query(3, O=19) == 0
+    assert L.halo_score_args_workspace_bytes(ctypes.byref(_lib.ScoreArgs(struct_bytes=8, B=B, H=H, W=W))) == 0
+    assert L.halo_score_args_workspace_bytes(ctypes.byref(_lib.ScoreArgs(struct_bytes=ctypes.sizeof(_lib.ScoreArgs), H=H, W=W))) == 0
     assert L.halo_hypermlr_workspace_bytes(19, 256) >= (3 * 19 + 2 * 19 * 256) * 8
     # the fused HyperMLR backward: a size for the shapes it serves (<= 20 classes, 64 | C <= 256), 0 = "use halo_hypermlr_bwd_terms" otherwise
     n = L.halo_hypermlr_backward_workspace_bytes(2, 64, 19, 160 * 320)
@@ -72,13 +95,71 @@ def test_workspace_queries_are_pure_host_functions():
     assert L.halo_select_workspace_bytes(0, 8, 8, 1, 1) == 0
 
 
+def test_score_args_layout_is_the_headers(tmp_path):
+    """_lib.ScoreArgs mirrors halo_score_args: a C11 program that includes include/halo_hip.h (so the header is valid plain C)
+    prints the struct's size and every field's offset as the host compiler lays them out; ctypes must agree on each, and the
+    field names stand in the same order in both declarations."""
+    import subprocess
+    from halo_amd import _build, _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "halo_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct halo_score_args \{(.*?)\} halo_score_args;", text, flags=re.S).group(1)
+    declared = [re.search(r"(\w+)\s*$", d).group(1) for stmt in body.split(";") if stmt.strip() for d in stmt.split(",")]
+    names = [f[0] for f in _lib.ScoreArgs._fields_]
+    assert declared == names
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "halo_hip.h"\nint main(void)\n{\n'
+                   '    printf("%zu\\n", sizeof(halo_score_args));\n'
+                   + "".join('    printf("%%zu\\n", offsetof(halo_score_args, %s));\n' % f for f in declared) + "    return 0;\n}\n")
+    cc = _build.host_cc()                                                      # the compiler _build.build_host uses
+    exe = str(tmp_path / "layout")
+    r = subprocess.run([cc, "-std=c11", "-Wall", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    assert got[0] == ctypes.sizeof(_lib.ScoreArgs)
+    assert got[1:] == [getattr(_lib.ScoreArgs, f).offset for f in names]
+
+
 def test_argument_errors_are_reported_not_crashed():
+    """Every case hands the scorer NULL outputs and a NULL workspace, or -- where a pointer is needed to reach the check -- 1-byte
+    HOST buffers and a workspace far too small: a check that went missing ends in another error code, never in a launch."""
     from halo_amd import _lib
     L = _lib.lib()
-    rc = L.halo_score_maps(None, 0, None, 0, 0, None, None, 1, 19, 0, 8, 8, 0, 4, 0, 3, 3, 100, 1.0, None, None, None,
-                           None, 0, None)
-    assert rc == -1 and b"null" in L.halo_last_error()
-    rc = L.halo_greedy_select(None, 1, 1, 8, 8, 1, 1, 5, None, None, None, None, None, None, None, 0, 0, None)
+    E_ARG, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
+    size = ctypes.sizeof(_lib.ScoreArgs)
+
+    def call(**kw):
+        fields = dict(struct_bytes=size, route=_lib.SCORE_FULL, B=1, O=19, H=8, W=8, unc_type=0, pur_type=4, ksize=3, pksize=3, K=100, c=1.0)
+        fields.update(kw)
+        rc = L.halo_score(ctypes.byref(_lib.ScoreArgs(**fields)), None)
+        return rc, L.halo_last_error()
+
+    rc, msg = call()                                                          # every pointer NULL
+    assert rc == E_ARG and b"null" in msg
+    assert L.halo_score(None, None) == E_ARG and b"null" in L.halo_last_error()
+    rc, msg = call(struct_bytes=size - 8)
+    assert rc == E_ARG and b"descriptor" in msg
+    rc, msg = call(route=3)
+    assert rc == E_ARG and b"route" in msg
+    rc, msg = call(route=_lib.SCORE_LR, hl=0, wl=4, hf=4, wf=4)
+    assert rc == E_ARG and b"low-res logit size" in msg
+    rc, msg = call(route=_lib.SCORE_LR_GRAM, hl=4, wl=4, hf=65536, wf=65536)
+    assert rc == E_UNSUPPORTED and b"2^31" in msg
+    rc, msg = call(flags=1 << 4)
+    assert rc == E_ARG and b"flag" in msg
+    # behind the null / empty check: logit, feat and score point at one host byte each, the workspace stays NULL and empty
+    byte = (ctypes.c_char * 1)()
+    host = dict(logit=ctypes.addressof(byte), feat=ctypes.addressof(byte), score=ctypes.addressof(byte), C=4)
+    rc, msg = call(ksize=4, **host)
+    assert rc == E_ARG and b"odd" in msg
+    rc, msg = call(pur_type=6, **host)
+    assert rc == E_UNSUPPORTED and b"not implemented" in msg
+    # one byte short of the base size, on a route whose 7 classes need far more: the base check reports it (were it gone, the
+    # check of the upsampled logits' share would still refuse the call, in other words)
+    need = L.halo_score_workspace_bytes(1, 8, 8)
+    rc, msg = call(route=_lib.SCORE_LR, O=7, hl=4, wl=4, hf=4, wf=4, workspace=ctypes.addressof(byte), workspace_bytes=need - 1, **host)
+    assert rc == E_WORKSPACE and msg == b"halo_score: workspace too small"
+    rc = L.halo_greedy_select(None, 1, 1, 8, 8, 1, 1, 5, None, None, None, None, None, None, None, 0, 0, None, None, None)
     assert rc == -1
 
 

@@ -1866,7 +1866,7 @@ def test_feature_kernel_chunk_map_is_invisible(dev):
 
 
 def test_scorer_tail_on_a_second_stream_equals_the_inline_call(dev):
-    """halo_score_maps_split: the passes over the inputs on the current stream, everything behind them on `tail_stream` (forked at
+    """halo_score_args.tail_stream: the passes over the inputs on the current stream, everything behind them on `tail_stream` (forked at
     the stop event) -- same bits as the one-stream call, for every branch that reads decoder_out, with the range record, several
     calls in flight on rotating workspaces."""
     from halo_amd import _lib
@@ -1909,6 +1909,34 @@ def test_scorer_tail_on_a_second_stream_equals_the_inline_call(dev):
         maps = (torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W), dtype=torch.float32, device=dev))
         ev = (L.halo_event_create(), L.halo_event_create())
         score_maps(lg, None, "entropy", "ripu", False, None, size=3, tail_stream=tail, events=ev, workspace=ws, maps=maps)   # no decoder_out pass to fork behind
+
+
+def test_lowres_optional_descriptor_fields_do_not_change_a_result(dev):
+    """halo_score_args' optional fields (the six events, score_range) on the low-res routes: the call that fills them all returns the
+    bits of the plain call.  (a) even source width, 8 float64 channels, 19 classes: the LDS-DMA feature kernel, the templated
+    logit kernel, the fused tail -- also through the Gram route; (b) 7 classes, 5 float32 channels, odd sizes: the generic class
+    count with its extra workspace, the register-staged feature kernel, the unfused tail."""
+    from halo_amd import _lib
+    from halo_amd.core.active.floating_region import new_score_range, score_maps_lowres
+    rng = np.random.default_rng(1117)
+    L = _lib.lib()
+    B = 2
+    for O, (h, w), C, dt, size, modes in ((19, (10, 18), 8, np.float64, (40, 72), ("exact", "gram")),
+                                          (7, (9, 13), 5, np.float32, (33, 49), ("exact",))):
+        logit = t(rng.standard_normal((B, O, h, w)).astype(np.float32), dev)
+        emb = t((rng.standard_normal((B, C, h, w)) * 0.05).astype(dt), dev)
+        for mode in modes:
+            kw = dict(unc_type="entropy", pur_type="hyper", normalize=True, K=8, mode=mode)
+            plain = score_maps_lowres(logit, emb, size, **kw)
+            ev = tuple(L.halo_event_create() for _ in range(6))
+            try:
+                full = score_maps_lowres(logit, emb, size, events=ev, score_range=new_score_range(B, dev), **kw)
+                torch.cuda.synchronize(dev)
+            finally:
+                for e in ev:
+                    L.halo_event_destroy(e)
+            for x, y in zip(plain, full):
+                assert torch.equal(x, y), (O, mode)
 
 
 def test_region_selection_full_size_real_geometry_vs_oracle(dev):
@@ -2912,7 +2940,7 @@ def test_headline_launch_shape_lowres_sources_batched_vs_oracle(dev):
 
 
 def test_sweep_hand_over_counters(dev):
-    """halo_greedy_select_ex's cost counters: which images the value-binned sweep finished, which it handed to the serial kernel,
+    """halo_greedy_select's cost counters (`handover`): which images the value-binned sweep finished, which it handed to the serial kernel,
     why, and after how many of its own picks -- with the picks identical to the oracle's either way.  A plateau of exact ties no
     longer hands the image over (round 4: any full bin did, from pick 0): below the values the picks need it is never reached, and
     reached it is walked in position order through the map itself."""
