@@ -99,6 +99,43 @@ def broadcast_or_resize(pooled, size, resize):
     return resize(pooled, size)
 
 
+def v3plus_decoder(self, pyramid, low, resize):
+    """The v3+ heads from the ASPP pyramid to the decoder's output (classifier.py:520-527): bottleneck, resize to the low-level
+    map, concat with the shortcut, decoder.  Both package forwards call it.
+
+    A head class marked by halo_amd.hooks.use_fused_decoder_front runs the front of the decoder -- the resize, the concat and the
+    depthwise half of decoder[0] -- as halo_amd.dwconv.upsample_cat_depthwise_bn_relu, which stores neither the resized nor the
+    concatenated tensor, then decoder[0]'s three pointwise modules and the remaining decoder modules unchanged.  That holds when
+    decoder[0] is a depthwise-separable block (the six DepthwiseSeparableConv2d attributes, an nn.ReLU depthwise_activate) inside
+    the operator's envelope (upcat_fallback_reason); any other marked instance, and every unmarked class, runs the statements
+    below.  A marked head returns what the same head returns under use_device_resize + use_fused_depthwise on that block, bit for
+    bit; that is not bit-equal to the stock F.interpolate / nn.Conv2d chain."""
+    if getattr(type(self), "_halo_fused_decoder_front", False):
+        from ...dwconv import upcat_fallback_reason, upsample_cat_depthwise_bn_relu
+        from ...hooks import _DWSEP_ATTRS
+        block = self.decoder[0] if isinstance(self.decoder, nn.Sequential) and len(self.decoder) > 0 else None
+        if block is not None and all(hasattr(block, a) for a in _DWSEP_ATTRS) and type(block.depthwise_activate) is nn.ReLU:
+            top = self.bottleneck(torch.cat(pyramid, dim=1))
+            short = self.shortcut(low)
+            if upcat_fallback_reason(top, short, block.depthwise_conv, block.depthwise_bn) is None:
+                dec = upsample_cat_depthwise_bn_relu(top, short, block.depthwise_conv, block.depthwise_bn)
+                dec = block.pointwise_activate(block.pointwise_bn(block.pointwise_conv(dec)))
+                for module in list(self.decoder)[1:]:
+                    dec = module(dec)
+                return dec
+            if resize is None:
+                fused = F.interpolate(top, size=low.shape[2:], mode="bilinear", align_corners=True)
+            else:
+                fused = resize(top, low.shape[2:])
+            return self.decoder(torch.cat([fused, short], dim=1))
+    if resize is None:
+        fused = self.bottleneck(torch.cat(pyramid, dim=1))
+        fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
+    else:
+        fused = resize(self.bottleneck(torch.cat(pyramid, dim=1)), low.shape[2:])
+    return self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
+
+
 def v2_hyper_forward(self, x, size=None):
     """forward of ASPP_Classifier_V2_Hyper (classifier.py:364-379): sum of the dilated 3x3 branches, HIP tail;
     DeepLab-v2 resizes the logits AND the embedding."""
@@ -120,12 +157,9 @@ def v3plus_hyper_forward(self, x, size=None):
     resize = device_resize(self)
     if resize is None:
         pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
-        fused = self.bottleneck(torch.cat(pyramid, dim=1))
-        fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
     else:
         pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
-        fused = resize(self.bottleneck(torch.cat(pyramid, dim=1)), low.shape[2:])
-    dec = self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
+    dec = v3plus_decoder(self, pyramid, low, resize)
     dec = self.conv_reduce(dec)
     if getattr(self, "wn_mlp", None) is not None:                      # classifier.py:531-550
         b, ch, h, w = dec.shape

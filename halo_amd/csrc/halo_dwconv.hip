@@ -22,7 +22,15 @@
 // and stores of a wave are contiguous.  An 80 x 160 plane at d = 6 / 12 / 18 is 240 / 480 / 720 threads with no halo row at
 // all; a 160 x 320 plane at d = 1 is 10 bands of 16 rows with a one-row halo either side.  A block works inside one plane, so
 // w, scale and shift are block-uniform.
+//
+// The decoder front (halo_upcat_*): the conv's input is cat([bilinear_align_corners(a, (H, W)), s], 1), d = 1, and neither the
+// resized nor the concatenated tensor exists.  A block works inside one plane, so which operand it reads is block-uniform: a
+// plane below Ca reads its window through DwUpSrc (the resize's own taps and bilerp, evaluated per window row), the others read
+// s through DwSrc.  Same DwGeom for C = Ca + Cs, same walk, same k_dw_wsum: the bits are those of the conv over the stored
+// concatenation.  The data gradient is written to two dense tensors split at plane Ca.
 #include "halo_common.hpp"
+#include "halo_devmath.hpp"
+#include "halo_softmax.hpp"
 
 namespace halo {
 
@@ -108,6 +116,84 @@ template <int MODE> struct DwSrc {
     }
 };
 
+// The operand of a plane below Ca of the decoder front: element (i, j) is the align_corners=True resize of the (h, w) plane `a`
+// to (H, W) -- bilerp over make_taps<float>(i, sh, h) / make_taps<float>(j, sw, w), halo_bilinear_upsample's expression, so its
+// bits -- and zero outside the plane.  d = 1 only.  bilerp interpolates along the columns first, and that half does not depend on
+// the output row: the thread keeps the column-interpolated values of the two source rows its last window row used (lo, hi), and
+// a row entering the window loads a source row only when its taps leave that pair -- at most one new row per output row when
+// walking down an upsampling.  A thread's GW + 2 columns (its own and the two neighbours) do not change down its segment: their
+// taps are computed once, a row's taps once per row entering the window.  Whether a source row is loaded is decided for the
+// whole wave (a load under a lane condition serialises); the loads themselves are unconditional from clamped addresses, and
+// the zero of the padding is selected afterwards.
+template <int GW> struct DwUpSrc {
+    const float *a;
+    int h, w;
+    float sh;
+    int x0[GW + 2], x1[GW + 2];
+    float lx0[GW + 2], lx1[GW + 2];
+    bool left_in, right_in;
+    int rl, rh;                      // the source rows held in lo and hi (-1: none yet)
+    float lo[GW + 2], hi[GW + 2];
+    __device__ __forceinline__ void init(const float *plane, int h_, int w_, float sh_, float sw, int c0, int W)
+    {
+        a = plane, h = h_, w = w_, sh = sh_;
+        left_in = c0 > 0, right_in = c0 + GW < W;
+        rl = rh = -1;
+#pragma unroll
+        for (int q = 0; q < GW + 2; ++q) {
+            int X = c0 - 1 + q;
+            X = X < 0 ? 0 : (X > W - 1 ? W - 1 : X);
+            const Taps<float> t = make_taps<float>(X, sw, w);
+            x0[q] = t.i0, x1[q] = t.i1, lx0[q] = t.l0, lx1[q] = t.l1;
+            lo[q] = hi[q] = 0.0f;
+        }
+    }
+    // bilerp's first half over source row r (0 <= r < h) at this thread's columns
+    __device__ __forceinline__ void source_row(float *v, int r) const
+    {
+        const float *p = a + (size_t)r * w;
+#pragma unroll
+        for (int q = 0; q < GW + 2; ++q) v[q] = col_lerp(lx0[q], lx1[q], p[x0[q]], p[x1[q]]);
+    }
+    // win[kx * GW + e] = the operand at (i, c0 + (kx - 1) + e)
+    template <int GWT, bool D1> __device__ __forceinline__ void row(float *win, int i, int c0, int H, int W, int d)
+    {
+        static_assert(GWT == GW, "one column group width per source");
+        const bool row_in = i >= 0 && i < H;
+        const Taps<float> ty = make_taps<float>(i < 0 ? 0 : (i > H - 1 ? H - 1 : i), sh, h);
+        const bool have0 = ty.i0 == rl || ty.i0 == rh, have1 = ty.i1 == rl || ty.i1 == rh;
+        float n0[GW + 2], n1[GW + 2];
+#pragma unroll
+        for (int q = 0; q < GW + 2; ++q) n0[q] = n1[q] = 0.0f;
+        if (__any(!have1)) source_row(n1, ty.i1);
+        if (__any(!have0 && ty.i0 != ty.i1)) source_row(n0, ty.i0);
+#pragma unroll
+        for (int q = 0; q < GW + 2; ++q) {
+            const float v1 = ty.i1 == rl ? lo[q] : (ty.i1 == rh ? hi[q] : n1[q]);
+            const float v0 = ty.i0 == rl ? lo[q] : (ty.i0 == rh ? hi[q] : (ty.i0 == ty.i1 ? n1[q] : n0[q]));
+            lo[q] = v0, hi[q] = v1;
+        }
+        rl = ty.i0, rh = ty.i1;
+        float v[GW + 2];
+#pragma unroll
+        for (int q = 0; q < GW + 2; ++q) {
+            const float e = col_lerp(ty.l0, ty.l1, lo[q], hi[q]);          // bilerp's second half
+            v[q] = row_in && (q > 0 || left_in) && (q < GW + 1 || right_in) ? e : 0.0f;
+        }
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+            for (int e = 0; e < GW; ++e) win[kx * GW + e] = v[kx + e];
+    }
+};
+
+// the operands of the decoder front: a (B, Ca, h, w) resized to (H, W) with the scales sh, sw in front of s (B, Cs, H, W)
+struct DwCat {
+    int Ca, Cs, h, w;
+    float sh, sw;
+    int c_lo, c_n;    // bwd_data: the channels [c_lo, c_lo + c_n) whose gradient is wanted
+};
+
 // this thread's column group and chain segment: false when it has none
 struct DwItem { int c0, i0, iend; };
 template <int GW> __device__ __forceinline__ bool dw_item(const DwGeom &G, int blk, DwItem &it)
@@ -125,28 +211,15 @@ template <int GW> __device__ __forceinline__ bool dw_item(const DwGeom &G, int b
     return true;
 }
 
-// MODE DW_FWD: a = x, out = y.  MODE DW_BWD: a = g, yv = y, out = g_x.
-template <int MODE, int GW, bool D1>
-__global__ void __launch_bounds__(DW_TPB) k_dw_apply(const float *__restrict__ a, const float *__restrict__ yv, const float *__restrict__ w,
-                                                     const float *__restrict__ scale, const float *__restrict__ shift, float *__restrict__ out, DwGeom G)
+// One thread's walk down its segment.  MODE DW_FWD: src = x, op = y.  MODE DW_BWD: src = gp, wk mirrored, op = g_x.
+template <int MODE, int GW, bool D1, typename SRC>
+__device__ __forceinline__ void dw_walk_apply(SRC &src, const float (&wk)[9], float sc, float sh, float *__restrict__ op, const DwItem &it,
+                                              const DwGeom &G)
 {
-    const long long plane = blockIdx.x / G.bpp;
-    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
-    DwItem it;
-    if (!dw_item<GW>(G, blk, it)) return;
-    const size_t po = (size_t)plane * G.H * G.W;
-    const float sc = scale[c];
-    DwSrc<MODE> src;
-    src.a = a + po, src.y = MODE == DW_BWD ? yv + po : nullptr, src.scale = sc;
-    float wk[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) wk[k] = MODE == DW_FWD ? w[c * 9 + k] : w[c * 9 + 8 - k];
-    const float sh = MODE == DW_FWD ? shift[c] : 0.0f;
     const int d = D1 ? 1 : G.d;
     float win[3][3 * GW];
     src.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
     src.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
-    float *op = out + po;
     for (int i = it.i0; i < it.iend; i += d) {
         src.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
         float res[GW];
@@ -174,42 +247,103 @@ __global__ void __launch_bounds__(DW_TPB) k_dw_apply(const float *__restrict__ a
     }
 }
 
-// part[(plane * bpp + blk) * 9 + k] = this block's float64 sum of gp[p] x[p + k d]
-template <int GW, bool D1>
-__global__ void __launch_bounds__(DW_TPB) k_dw_wpart(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ x,
-                                                     const float *__restrict__ scale, double *__restrict__ part, DwGeom G)
+// MODE DW_FWD: a = x, out = y.  MODE DW_BWD: a = g, yv = y, out = g_x.
+template <int MODE, int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dw_apply(const float *__restrict__ a, const float *__restrict__ yv, const float *__restrict__ w,
+                                                     const float *__restrict__ scale, const float *__restrict__ shift, float *__restrict__ out, DwGeom G)
 {
-    __shared__ double s[DW_TPB / 64][9];
     const long long plane = blockIdx.x / G.bpp;
     const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
-    const size_t po = (size_t)plane * G.H * G.W;
-    double acc[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
     DwItem it;
-    if (dw_item<GW>(G, blk, it)) {
-        DwSrc<DW_FWD> sx;
-        sx.a = x + po, sx.y = nullptr, sx.scale = 0.0f;
-        DwSrc<DW_BWD> sg;
-        sg.a = g + po, sg.y = yv + po, sg.scale = scale[c];
-        const int d = D1 ? 1 : G.d;
-        float win[3][3 * GW];
-        sx.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
-        sx.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
-        for (int i = it.i0; i < it.iend; i += d) {
-            sx.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
-            float gp[GW];
-            sg.template cols<GW, true>(gp, i, it.c0, G.H, G.W);
+    if (!dw_item<GW>(G, blk, it)) return;
+    const size_t po = (size_t)plane * G.H * G.W;
+    const float sc = scale[c];
+    DwSrc<MODE> src;
+    src.a = a + po, src.y = MODE == DW_BWD ? yv + po : nullptr, src.scale = sc;
+    float wk[9];
 #pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                const double ge = (double)gp[e];
+    for (int k = 0; k < 9; ++k) wk[k] = MODE == DW_FWD ? w[c * 9 + k] : w[c * 9 + 8 - k];
+    const float sh = MODE == DW_FWD ? shift[c] : 0.0f;
+    dw_walk_apply<MODE, GW, D1>(src, wk, sc, sh, out + po, it, G);
+}
+
+// The decoder front, forward: plane (b, c) of y from a's plane (b, c) resized in place (c < Ca) or from s's plane (b, c - Ca).
+template <int GW>
+__global__ void __launch_bounds__(DW_TPB) k_dw_upcat_fwd(const float *__restrict__ a, const float *__restrict__ s, const float *__restrict__ w,
+                                                         const float *__restrict__ scale, const float *__restrict__ shift, float *__restrict__ y,
+                                                         DwGeom G, DwCat K)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const long long b = plane / G.C;
+    DwItem it;
+    if (!dw_item<GW>(G, blk, it)) return;
+    const size_t hw = (size_t)G.H * G.W;
+    const float sc = scale[c], sh = shift[c];
+    float wk[9];
 #pragma unroll
-                for (int k = 0; k < 9; ++k) acc[k] = __builtin_fma(ge, (double)win[k / 3][(k % 3) * GW + e], acc[k]);
-            }
-#pragma unroll
-            for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
-        }
+    for (int k = 0; k < 9; ++k) wk[k] = w[c * 9 + k];
+    if (c < K.Ca) {
+        DwUpSrc<GW> src;
+        src.init(a + (size_t)(b * K.Ca + c) * K.h * K.w, K.h, K.w, K.sh, K.sw, it.c0, G.W);
+        dw_walk_apply<DW_FWD, GW, GW == 4>(src, wk, sc, sh, y + (size_t)plane * hw, it, G);
+    } else {
+        DwSrc<DW_FWD> src;
+        src.a = s + (size_t)(b * K.Cs + (c - K.Ca)) * hw, src.y = nullptr, src.scale = sc;
+        dw_walk_apply<DW_FWD, GW, GW == 4>(src, wk, sc, sh, y + (size_t)plane * hw, it, G);
     }
+}
+
+// The decoder front, data gradient: the planes [c_lo, c_lo + c_n) of dw3x3^T(gp), those below Ca into g_up (B, Ca, H, W), the
+// others into g_s (B, Cs, H, W).
+template <int GW>
+__global__ void __launch_bounds__(DW_TPB) k_dw_upcat_bwd(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ w,
+                                                         const float *__restrict__ scale, float *__restrict__ g_up, float *__restrict__ g_s,
+                                                         DwGeom G, DwCat K)
+{
+    const long long q = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - q * G.bpp), c = K.c_lo + (int)(q % K.c_n);
+    const long long b = q / K.c_n;
+    DwItem it;
+    if (!dw_item<GW>(G, blk, it)) return;
+    const size_t hw = (size_t)G.H * G.W, po = (size_t)(b * G.C + c) * hw;
+    const float sc = scale[c];
+    DwSrc<DW_BWD> src;
+    src.a = g + po, src.y = yv + po, src.scale = sc;
+    float wk[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wk[k] = w[c * 9 + 8 - k];
+    float *op = c < K.Ca ? g_up + (size_t)(b * K.Ca + c) * hw : g_s + (size_t)(b * K.Cs + (c - K.Ca)) * hw;
+    dw_walk_apply<DW_BWD, GW, GW == 4>(src, wk, sc, 0.0f, op, it, G);
+}
+
+// One thread's float64 sums of gp[p] x[p + k d] over its segment: rows ascending, per row columns ascending
+template <int GW, bool D1, typename SX>
+__device__ __forceinline__ void dw_walk_wpart(SX &sx, const DwSrc<DW_BWD> &sg, const DwItem &it, const DwGeom &G, double (&acc)[9])
+{
+    const int d = D1 ? 1 : G.d;
+    float win[3][3 * GW];
+    sx.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
+    sx.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
+    for (int i = it.i0; i < it.iend; i += d) {
+        sx.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
+        float gp[GW];
+        sg.template cols<GW, true>(gp, i, it.c0, G.H, G.W);
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            const double ge = (double)gp[e];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) acc[k] = __builtin_fma(ge, (double)win[k / 3][(k % 3) * GW + e], acc[k]);
+        }
+#pragma unroll
+        for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
+    }
+}
+
+// part[blockIdx.x * 9 + k] = the block's sum: its threads by a fixed shuffle tree, its four waves in ascending order
+__device__ __forceinline__ void dw_block_sum(const double (&acc)[9], double *__restrict__ part)
+{
+    __shared__ double s[DW_TPB / 64][9];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
@@ -224,6 +358,58 @@ __global__ void __launch_bounds__(DW_TPB) k_dw_wpart(const float *__restrict__ g
         for (int q = 1; q < DW_TPB / 64; ++q) t += s[q][threadIdx.x];
         part[(size_t)blockIdx.x * 9 + threadIdx.x] = t;
     }
+}
+
+// part[(plane * bpp + blk) * 9 + k] = this block's float64 sum of gp[p] x[p + k d]
+template <int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dw_wpart(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ x,
+                                                     const float *__restrict__ scale, double *__restrict__ part, DwGeom G)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const size_t po = (size_t)plane * G.H * G.W;
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    DwItem it;
+    if (dw_item<GW>(G, blk, it)) {
+        DwSrc<DW_FWD> sx;
+        sx.a = x + po, sx.y = nullptr, sx.scale = 0.0f;
+        DwSrc<DW_BWD> sg;
+        sg.a = g + po, sg.y = yv + po, sg.scale = scale[c];
+        dw_walk_wpart<GW, D1>(sx, sg, it, G, acc);
+    }
+    dw_block_sum(acc, part);
+}
+
+// The decoder front, weight gradient: the same rows of `part`, x recomputed from a (c < Ca) or read from s.
+template <int GW>
+__global__ void __launch_bounds__(DW_TPB) k_dw_upcat_wpart(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ a,
+                                                           const float *__restrict__ s, const float *__restrict__ scale, double *__restrict__ part,
+                                                           DwGeom G, DwCat K)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const long long b = plane / G.C;
+    const size_t hw = (size_t)G.H * G.W, po = (size_t)plane * hw;
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    DwItem it;
+    if (dw_item<GW>(G, blk, it)) {
+        DwSrc<DW_BWD> sg;
+        sg.a = g + po, sg.y = yv + po, sg.scale = scale[c];
+        if (c < K.Ca) {
+            DwUpSrc<GW> sx;
+            sx.init(a + (size_t)(b * K.Ca + c) * K.h * K.w, K.h, K.w, K.sh, K.sw, it.c0, G.W);
+            dw_walk_wpart<GW, GW == 4>(sx, sg, it, G, acc);
+        } else {
+            DwSrc<DW_FWD> sx;
+            sx.a = s + (size_t)(b * K.Cs + (c - K.Ca)) * hw, sx.y = nullptr, sx.scale = 0.0f;
+            dw_walk_wpart<GW, GW == 4>(sx, sg, it, G, acc);
+        }
+    }
+    dw_block_sum(acc, part);
 }
 
 // g_w[c, k] = sum over images b, then blocks, in ascending order
@@ -271,6 +457,27 @@ static void dw_launch_apply(bool vec, unsigned grid, hipStream_t st, const float
     if (vec && G.d == 1) hipLaunchKernelGGL((k_dw_apply<MODE, 4, true>), g, b, 0, st, a, yv, w, scale, shift, out, G);
     else if (vec) hipLaunchKernelGGL((k_dw_apply<MODE, 4, false>), g, b, 0, st, a, yv, w, scale, shift, out, G);
     else hipLaunchKernelGGL((k_dw_apply<MODE, 1, false>), g, b, 0, st, a, yv, w, scale, shift, out, G);
+}
+
+// the decoder front's shapes: dw_check for C = Ca + Cs at d = 1, then the resize's own conditions
+static int upcat_check(const char *who, int64_t B, int64_t Ca, int64_t Cs, int64_t h, int64_t w, int64_t H, int64_t W)
+{
+    if (Ca < 0 || Cs < 0 || h < 1 || w < 1) return fail(HALO_E_ARG, "%s: empty shape", who);
+    if (int rc = dw_check(who, B, Ca + Cs, H, W, 1)) return rc;
+    if (H < h || W < w)
+        return fail(HALO_E_ARG, "%s: the planes of s, %lld x %lld, are smaller than a's %lld x %lld (an upsampling only)", who, (long long)H,
+                    (long long)W, (long long)h, (long long)w);
+    return HALO_OK;
+}
+
+static DwCat upcat_operands(int64_t Ca, int64_t Cs, int64_t h, int64_t w, int64_t H, int64_t W)
+{
+    DwCat K;
+    K.Ca = (int)Ca, K.Cs = (int)Cs, K.h = (int)h, K.w = (int)w;
+    // halo_bilinear_upsample's scales (launch_bilinear_rows, halo_hyperbolic.hip)
+    K.sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f, K.sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
+    K.c_lo = 0, K.c_n = (int)(Ca + Cs);
+    return K;
 }
 
 }  // namespace halo
@@ -332,6 +539,71 @@ extern "C" int halo_dwconv3x3_affine_relu_bwd_weight(const float *g, const float
     if (vec && d == 1) hipLaunchKernelGGL((k_dw_wpart<4, true>), gr, bl, 0, st, g, y, x, scale, part, G);
     else if (vec) hipLaunchKernelGGL((k_dw_wpart<4, false>), gr, bl, 0, st, g, y, x, scale, part, G);
     else hipLaunchKernelGGL((k_dw_wpart<1, false>), gr, bl, 0, st, g, y, x, scale, part, G);
+    hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
+    return check_launch(who);
+}
+
+extern "C" int halo_upcat_dwconv3x3_affine_relu_fwd(const float *a, const float *s, const float *w, const float *scale, const float *shift,
+                                                    float *y, int64_t B, int64_t Ca, int64_t Cs, int64_t h, int64_t w_in, int64_t H, int64_t W,
+                                                    void *stream)
+{
+    const char *who = "halo_upcat_dwconv3x3_affine_relu_fwd";
+    if (int rc = upcat_check(who, B, Ca, Cs, h, w_in, H, W)) return rc;
+    if ((Ca > 0 && !a) || (Cs > 0 && !s) || !w || !scale || !shift || !y) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = dw_vec(W, s, y, nullptr, nullptr);
+    const DwGeom G = dw_geom(Ca + Cs, H, W, 1, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * (Ca + Cs), G, grid)) return rc;
+    const DwCat K = upcat_operands(Ca, Cs, h, w_in, H, W);
+    const dim3 gr(grid), bl(DW_TPB);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL((k_dw_upcat_fwd<4>), gr, bl, 0, st, a, s, w, scale, shift, y, G, K);
+    else hipLaunchKernelGGL((k_dw_upcat_fwd<1>), gr, bl, 0, st, a, s, w, scale, shift, y, G, K);
+    return check_launch(who);
+}
+
+extern "C" int halo_upcat_dwconv3x3_affine_relu_bwd_data(const float *g, const float *y, const float *w, const float *scale, float *g_up,
+                                                         float *g_s, int64_t B, int64_t Ca, int64_t Cs, int64_t H, int64_t W, void *stream)
+{
+    const char *who = "halo_upcat_dwconv3x3_affine_relu_bwd_data";
+    if (int rc = upcat_check(who, B, Ca, Cs, 1, 1, H, W)) return rc;
+    if (!g || !y || !w || !scale) return fail(HALO_E_ARG, "%s: null argument", who);
+    DwCat K = upcat_operands(Ca, Cs, 1, 1, H, W);
+    K.c_lo = g_up ? 0 : (int)Ca;
+    K.c_n = (int)((g_up ? Ca : 0) + (g_s ? Cs : 0));
+    if (K.c_n == 0) return HALO_OK;                                // no gradient wanted (or none of the wanted half's channels exist)
+    const bool vec = dw_vec(W, g, y, g_up, g_s);
+    const DwGeom G = dw_geom(Ca + Cs, H, W, 1, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * K.c_n, G, grid)) return rc;
+    const dim3 gr(grid), bl(DW_TPB);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL((k_dw_upcat_bwd<4>), gr, bl, 0, st, g, y, w, scale, g_up, g_s, G, K);
+    else hipLaunchKernelGGL((k_dw_upcat_bwd<1>), gr, bl, 0, st, g, y, w, scale, g_up, g_s, G, K);
+    return check_launch(who);
+}
+
+extern "C" int halo_upcat_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const float *a, const float *s, const float *scale,
+                                                           float *g_w, int64_t B, int64_t Ca, int64_t Cs, int64_t h, int64_t w_in, int64_t H,
+                                                           int64_t W, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "halo_upcat_dwconv3x3_affine_relu_bwd_weight";
+    if (int rc = upcat_check(who, B, Ca, Cs, h, w_in, H, W)) return rc;
+    if (!g || !y || (Ca > 0 && !a) || (Cs > 0 && !s) || !scale || !g_w) return fail(HALO_E_ARG, "%s: null argument", who);
+    const int64_t C = Ca + Cs;
+    const size_t need = halo_dwconv_workspace_bytes(B, C, H, W, 1);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 8) != 0)
+        return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (8-byte aligned)", who, workspace_bytes, need);
+    const bool vec = dw_vec(W, g, y, s, nullptr);
+    const DwGeom G = dw_geom(C, H, W, 1, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    const DwCat K = upcat_operands(Ca, Cs, h, w_in, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    const dim3 gr(grid), bl(DW_TPB);
+    if (vec) hipLaunchKernelGGL((k_dw_upcat_wpart<4>), gr, bl, 0, st, g, y, a, s, scale, part, G, K);
+    else hipLaunchKernelGGL((k_dw_upcat_wpart<1>), gr, bl, 0, st, g, y, a, s, scale, part, G, K);
     hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
     return check_launch(who);
 }

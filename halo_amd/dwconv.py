@@ -19,6 +19,13 @@ eval mode with running statistics whose parameters need no gradient: scale = wei
 Anything outside the served envelope (fallback_reason) runs the three stock module calls (torch_statement), so torch's results
 and errors are kept there: batch statistics, a conv bias, other kernel sizes / strides / padding, other dtypes, autocast, CPU
 tensors.
+
+The front of the v3+ decoder feeds such a block with `torch.cat([resize(a, s.shape[2:]), s], 1)`.
+`upsample_cat_depthwise_bn_relu(a, s, conv, bn)` computes that block's depthwise half without storing the resized or the
+concatenated tensor: the kernel reads its window from a (interpolated in place, halo_bilinear_upsample's bits) or from s, the
+backward keeps a, s and y, recomputes the conv's input for the weight gradient and writes the data gradient as two dense tensors,
+the first of which halo_bilinear_upsample_bwd turns into g_a.  Its results are those of depthwise_bn_relu over the stored
+concatenation, bit for bit; outside its envelope (upcat_fallback_reason) it runs that composition.
 """
 import torch
 import torch.nn as nn
@@ -44,59 +51,73 @@ def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
-def fallback_reason(x, conv, bn):
-    """why depthwise_bn_relu(x, conv, bn) runs the torch statements (None: the fused path serves it).  Reads no device memory."""
+def _module_reason(conv, bn):
+    """(reason, the norm's tensors): the part of fallback_reason that looks at the modules alone"""
     if type(conv) is not nn.Conv2d:
-        return "conv is not nn.Conv2d"
+        return "conv is not nn.Conv2d", None
     C = conv.in_channels
     if conv.groups != C or conv.out_channels != C:
-        return "conv is not depthwise (groups == in_channels == out_channels)"
+        return "conv is not depthwise (groups == in_channels == out_channels)", None
     if _pair(conv.kernel_size) != (3, 3):
-        return "kernel size %s, not (3, 3)" % (tuple(_pair(conv.kernel_size)),)
+        return "kernel size %s, not (3, 3)" % (tuple(_pair(conv.kernel_size)),), None
     if _pair(conv.stride) != (1, 1):
-        return "stride %s, not 1" % (tuple(_pair(conv.stride)),)
+        return "stride %s, not 1" % (tuple(_pair(conv.stride)),), None
     dil = _pair(conv.dilation)
     if isinstance(conv.padding, str) or dil[0] != dil[1] or dil[0] < 1 or _pair(conv.padding) != dil:
-        return "dilation %s and padding %s are not one (d, d)" % (conv.dilation, conv.padding)
+        return "dilation %s and padding %s are not one (d, d)" % (conv.dilation, conv.padding), None
     if conv.padding_mode != "zeros":
-        return "padding_mode %r" % conv.padding_mode
+        return "padding_mode %r" % conv.padding_mode, None
     if conv.bias is not None:
-        return "conv has a bias"
+        return "conv has a bias", None
     if _is_frozen(bn):
         tensors = [bn.weight, bn.bias, bn.running_mean, bn.running_var]
         features = bn.weight.numel()
     elif type(bn) in (nn.BatchNorm2d, nn.SyncBatchNorm):
         if bn.training or bn.running_mean is None or bn.running_var is None:
-            return "BatchNorm with batch statistics"
+            return "BatchNorm with batch statistics", None
         if (bn.weight is None) != (bn.bias is None):
-            return "BatchNorm with only one of weight and bias"
+            return "BatchNorm with only one of weight and bias", None
         if torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in (bn.weight, bn.bias)):
-            return "BatchNorm parameters require a gradient"
+            return "BatchNorm parameters require a gradient", None
         tensors = [bn.weight, bn.bias, bn.running_mean, bn.running_var]
         features = bn.num_features
     else:
-        return "bn is neither a FrozenBatchNorm2d nor an eval-mode BatchNorm2d / SyncBatchNorm"
+        return "bn is neither a FrozenBatchNorm2d nor an eval-mode BatchNorm2d / SyncBatchNorm", None
     if features != C:
-        return "the norm has %d channels, the conv %d" % (features, C)
-    if not torch.is_tensor(x) or x.dim() != 4:
-        return "x is not a (B, C, H, W) tensor"
-    if x.shape[1] != C:
-        return "x has %d channels, the conv %d" % (x.shape[1], C)
-    if x.dtype != torch.float32:
-        return "x is %s, not float32" % x.dtype
+        return "the norm has %d channels, the conv %d" % (features, C), None
+    return None, tensors
+
+
+def _operand_reason(shape, dtype, is_cuda, device, conv, tensors):
+    """the part of fallback_reason that looks at the conv's input, given as its (B, C, H, W) shape, dtype and placement"""
+    C, dil = conv.in_channels, _pair(conv.dilation)
+    if shape[1] != C:
+        return "x has %d channels, the conv %d" % (shape[1], C)
+    if dtype != torch.float32:
+        return "x is %s, not float32" % dtype
     if _autocast():
         return "autocast is enabled"
-    if not x.is_cuda:
+    if not is_cuda:
         return "x is not on a ROCm device"
     for t in [conv.weight] + tensors:
-        if t is not None and (t.dtype != torch.float32 or t.device != x.device):
-            return "a conv / norm tensor is not float32 on %s" % x.device
-    B, _, H, W = x.shape
+        if t is not None and (t.dtype != torch.float32 or t.device != device):
+            return "a conv / norm tensor is not float32 on %s" % device
+    B, _, H, W = shape
     if B * C * H * W == 0:
         return "empty input"
     if max(H, W, dil[0]) > 1 << 24 or H * W > 2 ** 31 - 1:
         return "plane of %d x %d, dilation %d" % (H, W, dil[0])
     return None
+
+
+def fallback_reason(x, conv, bn):
+    """why depthwise_bn_relu(x, conv, bn) runs the torch statements (None: the fused path serves it).  Reads no device memory."""
+    why, tensors = _module_reason(conv, bn)
+    if why is not None:
+        return why
+    if not torch.is_tensor(x) or x.dim() != 4:
+        return "x is not a (B, C, H, W) tensor"
+    return _operand_reason(tuple(x.shape), x.dtype, x.is_cuda, x.device, conv, tensors)
 
 
 def scale_shift(bn):
@@ -159,4 +180,90 @@ def depthwise_bn_relu(x, conv, bn, act=None):
     return _DepthwiseBnReluFn.apply(x.contiguous(), conv.weight.contiguous(), scale, shift, int(_pair(conv.dilation)[0]))
 
 
-__all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift"]
+def upcat_fallback_reason(a, s, conv, bn):
+    """why upsample_cat_depthwise_bn_relu(a, s, conv, bn) runs the composition (None: the fused path serves it).  Reads no device
+    memory."""
+    why, tensors = _module_reason(conv, bn)
+    if why is not None:
+        return why
+    if _pair(conv.dilation) != (1, 1):
+        return "dilation %s, not 1" % (conv.dilation,)
+    for name, t in (("a", a), ("s", s)):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            return "%s is not a (B, C, H, W) tensor" % name
+        if t.dtype != torch.float32:
+            return "%s is %s, not float32" % (name, t.dtype)
+        if not t.is_cuda:
+            return "%s is not on a ROCm device" % name
+    if a.device != s.device:
+        return "a is on %s, s on %s" % (a.device, s.device)
+    (B, Ca, h, w), (Bs, Cs, H, W) = a.shape, s.shape
+    if B != Bs:
+        return "a has %d images, s %d" % (B, Bs)
+    if B * Ca * h * w == 0 or B * Cs * H * W == 0:
+        return "empty input"
+    if H < h or W < w:
+        return "s's planes %s are smaller than a's %s: an upsampling only" % ((H, W), (h, w))
+    if B * Ca > 1 << 40:                     # halo_bilinear_upsample_bwd's plane count; its H and W limits lie above dw_check's
+        return "%d planes to resize" % (B * Ca)
+    return _operand_reason((B, Ca + Cs, H, W), torch.float32, True, s.device, conv, tensors)   # the concatenated tensor, which is never made
+
+
+class _UpCatDepthwiseBnReluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, s, w, scale, shift):
+        (B, Ca, h, wi), (_, Cs, H, W) = a.shape, s.shape
+        L = _lib.lib()
+        y = torch.empty((B, Ca + Cs, H, W), dtype=torch.float32, device=s.device)
+        _lib.check(L.halo_upcat_dwconv3x3_affine_relu_fwd(_lib.ptr(a), _lib.ptr(s), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y),
+                                                          B, Ca, Cs, h, wi, H, W, _lib.stream_ptr(s.device)),
+                   "halo_upcat_dwconv3x3_affine_relu_fwd")
+        ctx.save_for_backward(a, s, y, w, scale)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        a, s, y, w, scale = ctx.saved_tensors
+        (B, Ca, h, wi), (_, Cs, H, W) = a.shape, s.shape
+        L = _lib.lib()
+        st = _lib.stream_ptr(s.device)
+        g = g.to(device=s.device, dtype=torch.float32).contiguous()
+        need_a, need_s, need_w = ctx.needs_input_grad[:3]
+        ga = gs = gw = None
+        if need_a or need_s:
+            gup = torch.empty((B, Ca, H, W), dtype=torch.float32, device=s.device) if need_a else None
+            gs = torch.empty_like(s) if need_s else None
+            _lib.check(L.halo_upcat_dwconv3x3_affine_relu_bwd_data(_lib.ptr(g), _lib.ptr(y), _lib.ptr(w), _lib.ptr(scale),
+                                                                   _lib.ptr(gup) if need_a else None, _lib.ptr(gs) if need_s else None,
+                                                                   B, Ca, Cs, H, W, st), "halo_upcat_dwconv3x3_affine_relu_bwd_data")
+            if need_a:
+                ga = torch.empty_like(a)
+                _lib.check(L.halo_bilinear_upsample_bwd(_lib.ptr(gup), _lib.ptr(ga), _lib.dtype_code(gup), B * Ca, h, wi, H, W, st),
+                           "halo_bilinear_upsample_bwd")
+                del gup
+        if need_w:
+            nws = L.halo_dwconv_workspace_bytes(B, Ca + Cs, H, W, 1)
+            ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=s.device)
+            gw = torch.empty_like(w)
+            _lib.check(L.halo_upcat_dwconv3x3_affine_relu_bwd_weight(_lib.ptr(g), _lib.ptr(y), _lib.ptr(a), _lib.ptr(s), _lib.ptr(scale),
+                                                                     _lib.ptr(gw), B, Ca, Cs, h, wi, H, W, _lib.ptr(ws), ws.numel() * 8, st),
+                       "halo_upcat_dwconv3x3_affine_relu_bwd_weight")
+        return ga, gs, gw, None, None
+
+
+def upsample_cat_depthwise_bn_relu(a, s, conv, bn, act=None):
+    """relu(bn(conv(cat([resize(a, s.shape[2:]), s], 1)))) for a (B, Ca, h, w), s (B, Cs, H, W), a depthwise 3x3 conv of Ca + Cs
+    channels at dilation 1 and a frozen / eval-mode norm: y (B, Ca + Cs, H, W), the resize bilinear with align_corners=True.
+    Neither the resized nor the concatenated tensor is stored, forward or backward.  Differentiable once w.r.t. a, s and
+    conv.weight.  The bits are those of depthwise_bn_relu(torch.cat([bilinear_resize(a, (H, W)), s], 1), conv, bn): not those of
+    the stock F.interpolate / nn.Conv2d chain.  Outside the served envelope (upcat_fallback_reason) it returns
+    depthwise_bn_relu(torch.cat([resize_or_interpolate(a, (H, W)), s], 1), conv, bn, act), which has its own fallbacks."""
+    if upcat_fallback_reason(a, s, conv, bn) is not None:
+        from .resize import resize_or_interpolate
+        return depthwise_bn_relu(torch.cat([resize_or_interpolate(a, tuple(s.shape[2:])), s], 1), conv, bn, act)
+    scale, shift = scale_shift(bn)
+    return _UpCatDepthwiseBnReluFn.apply(a.contiguous(), s.contiguous(), conv.weight.contiguous(), scale, shift)
+
+
+__all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift", "upsample_cat_depthwise_bn_relu", "upcat_fallback_reason"]

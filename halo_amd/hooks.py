@@ -286,7 +286,7 @@ def use_fused_training_losses(learner_cls):
 # kept as `_unfused_forward`.  Neither install() nor the existing forward changes.
 
 def fused_v3plus_hyper_forward(self, x, size=None):
-    from .core.models.classifier import _tail_modules, broadcast_or_resize, device_resize, hyper_head_tail
+    from .core.models.classifier import _tail_modules, broadcast_or_resize, device_resize, hyper_head_tail, v3plus_decoder
     from .hfr import weighted_normalize
     low, top = x["low"], x["out"]
     pyramid = [branch(top) for branch in self.parallel_branches]
@@ -294,12 +294,9 @@ def fused_v3plus_hyper_forward(self, x, size=None):
     resize = device_resize(self)
     if resize is None:
         pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
-        fused = self.bottleneck(torch.cat(pyramid, dim=1))
-        fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
     else:
         pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
-        fused = resize(self.bottleneck(torch.cat(pyramid, dim=1)), low.shape[2:])
-    dec = self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
+    dec = v3plus_decoder(self, pyramid, low, resize)
     dec = self.conv_reduce(dec)
     if getattr(self, "wn_mlp", None) is not None:
         dec = weighted_normalize(dec, self.wn_mlp)
@@ -390,6 +387,28 @@ def use_fused_depthwise(block_cls):
     block_cls._unfused_forward = _inherited(block_cls, "forward")
     block_cls.forward = fused_dwsep_forward
     return block_cls
+
+
+# ---------------------------------------------------------------- the front of the v3+ decoder in one pass
+# Both v3+ forwards resize the bottleneck's output to the low-level map, concatenate it with the shortcut and hand the result to
+# decoder[0], whose depthwise half reads it once: at the training crop a 210 MB and a 229 MB tensor that exist only to be read
+# again.  `use_fused_decoder_front(head_cls)` marks a head class that carries one of the package's v3+ forwards; its instances run
+# halo_amd.dwconv.upsample_cat_depthwise_bn_relu there (core.models.classifier.v3plus_decoder: the condition, the order of the
+# module calls and the fallback).  A class attribute like use_device_resize's: opt-in, not bound by install(), composes with the
+# other hooks in any order; parameters, module names and state_dict() are untouched.
+
+def use_fused_decoder_front(head_cls):
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward or fused_v3plus_hyper_forward) so that the resize, the concat
+    and the depthwise half of decoder[0] run as one HIP pass.  Returns the class.  Idempotent.  The marked head's results are
+    those of the head under use_device_resize + use_fused_depthwise on that block, bit for bit -- not those of the stock
+    F.interpolate / nn.Conv2d chain."""
+    if not isinstance(head_cls, type):
+        raise TypeError("use_fused_decoder_front: expected a class, got %r" % (head_cls,))
+    if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
+        raise TypeError("use_fused_decoder_front: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
+                        "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
+    head_cls._halo_fused_decoder_front = True
+    return head_cls
 
 
 # ---------------------------------------------------------------- frozen norm + residual add + ReLU of the backbone and the heads

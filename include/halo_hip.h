@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 11
+#define HALO_ABI_VERSION 12
 
 enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4 };
 
@@ -426,6 +426,26 @@ int halo_dwconv3x3_affine_relu_bwd_data(const float *g, const float *y, const fl
 int halo_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const float *x, const float *scale, float *g_w, int64_t B,
                                           int64_t C, int64_t H, int64_t W, int64_t d, void *workspace, size_t workspace_bytes,
                                           void *stream);
+
+/* ---- the front of the v3+ decoder: resize + concat + depthwise 3x3 conv + frozen norm + ReLU in one pass ----
+ *  a (B, Ca, h, w), s (B, Cs, H, W) with H >= h, W >= w, y and g (B, Ca + Cs, H, W), g_up (B, Ca, H, W), g_s (B, Cs, H, W): f32 dense
+ *  NCHW; w (Ca + Cs, 1, 3, 3), scale, shift (Ca + Cs) f32; dilation = padding = 1.
+ *    x[b,c] = c < Ca ? bilinear_align_corners(a[b,c], (H, W)) : s[b,c-Ca]      (never stored: halo_bilinear_upsample's bits)
+ *    y = the forward above over x;  gp = g [y > 0] scale;  g_up | g_s = the planes below | from Ca of sum_k w[c,k] gp[p - k];
+ *    g_w[c,k] = sum_{b,p} gp x[p + k]  (x recomputed from a / s)
+ *  Same summation orders and the same work split as the calls above for C = Ca + Cs, d = 1, so y, g_up | g_s and g_w carry the
+ *  bits those calls return for the stored concatenation.  g_a is halo_bilinear_upsample_bwd(g_up).  bwd_data: either output may
+ *  be NULL, its planes are then skipped; with both NULL nothing is launched.  a may be NULL when Ca = 0, s when Cs = 0.  16-byte
+ *  loads and stores when W % 4 == 0 and s, y, g, g_up, g_s are 16-byte aligned, one column per thread otherwise: the same bits.
+ *  bwd_weight's workspace: halo_dwconv_workspace_bytes(B, Ca + Cs, H, W, 1).  HALO_E_ARG: a missing pointer, an empty shape
+ *  (Ca + Cs = 0 included), H < h or W < w; HALO_E_UNSUPPORTED: the limits above; HALO_E_WORKSPACE: a short workspace. */
+int halo_upcat_dwconv3x3_affine_relu_fwd(const float *a, const float *s, const float *w, const float *scale, const float *shift, float *y,
+                                         int64_t B, int64_t Ca, int64_t Cs, int64_t h, int64_t w_in, int64_t H, int64_t W, void *stream);
+int halo_upcat_dwconv3x3_affine_relu_bwd_data(const float *g, const float *y, const float *w, const float *scale, float *g_up, float *g_s,
+                                              int64_t B, int64_t Ca, int64_t Cs, int64_t H, int64_t W, void *stream);
+int halo_upcat_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const float *a, const float *s, const float *scale,
+                                                float *g_w, int64_t B, int64_t Ca, int64_t Cs, int64_t h, int64_t w_in, int64_t H, int64_t W,
+                                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- frozen norm + residual add + ReLU of a ResNet block (core/models/resnet.py:53-69, 92-112; core/models/layers.py) ----
  *  x, r, y, g, g_x, g_r (B, C, HW) f32 dense NCHW planes; scale, shift, r_scale, r_shift (C) f32.
