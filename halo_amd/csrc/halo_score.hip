@@ -19,6 +19,7 @@
 #include "halo_select_plan.hpp"      // SelHdr / order_key: the score-range record handed to the selector
 #include "halo_softmax.hpp"           // Taps / make_taps, softmax_lean / softmax_general (shared with halo_eval.hip)
 #include <stdlib.h>
+#include <type_traits>
 
 namespace halo {
 
@@ -1111,6 +1112,100 @@ constexpr int LR_TW = 64, LR_TH = 16, LR_PPT = 4;   // 64 x 16 output pixels per
 // The four taps are combined by bilerp (halo_devmath.hpp): columns first, rows second -- ATen's order.
 template <typename T, int NPX = LR_PPT> struct LrW { T lx0, lx1, ly0[NPX], ly1[NPX]; };
 
+// Tile <-> block: workgroups go to the 8 XCDs round-robin in launch order, each XCD with its own L2.  Tiles that are
+// neighbours along x share the source lines at their common border (a tile's 19-element window rows straddle two
+// 128-byte lines), so in launch order every line would be fetched by two XCDs.  Give the blocks that share an XCD
+// (id % 8) one contiguous eighth of the row-major tile list instead -- bijective for any tile count.
+struct LrTile { unsigned id; int b, X0, Y0; };      // tile in the launch's row-major list, image, first output pixel
+template <int TH> __device__ __forceinline__ LrTile lr_tile()
+{
+    const unsigned ntx = gridDim.x, nty = gridDim.y, ntiles = ntx * nty * gridDim.z;
+    const unsigned lin = blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z);
+    const unsigned xq = ntiles / 8, xr = ntiles % 8, xk = lin % 8;
+    const unsigned id = (xk < xr ? xk * (xq + 1) : xr * (xq + 1) + (xk - xr) * xq) + lin / 8;
+    return {id, (int)(id / (ntx * nty)), (int)(id % ntx) * LR_TW, (int)((id / ntx) % nty) * TH};
+}
+
+// A lane's NPX vertically adjacent output pixels (column X0 + lane, rows Y0 + wave * NPX + j): weights, accumulators, the
+// offsets of each pixel's upper-left and lower-left tap inside one channel plane of the window that starts at source
+// (ty_lo, tx_lo) with `stride` elements per row, and the wave's row code.
+template <typename T, int NPX = LR_PPT> struct LrLane {
+    LrW<T, NPX> wt;
+    T acc[NPX];
+    int o00[NPX], o10[NPX], dx1;
+    bool live[NPX];
+    int upat;        // wave-uniform row code: LrRows' PAT (1 bit per pixel) for LR_PPT pixels, LrRowsImmN's CODE (2 bits) above; -1: neither fits
+    __device__ __forceinline__ void setup(const LrTile &t, int H, int W, T sh, T sw, int h, int w, int ty_lo, int tx_lo, int stride)
+    {
+        const int x = t.X0 + (int)(threadIdx.x & (LR_TW - 1)), ly = threadIdx.x / LR_TW;      // ly = wave in 0..3
+        const bool xin = x < W;
+        const Taps<T> tx = make_taps<T>(xin ? x : W - 1, sw, w);
+        wt.lx0 = tx.l0; wt.lx1 = tx.l1;
+        int a0 = 0, pat = 0;
+        bool regular = true;
+#pragma unroll
+        for (int j = 0; j < NPX; ++j) {
+            const int y = t.Y0 + ly * NPX + j;
+            live[j] = xin && y < H;
+            const Taps<T> ty = make_taps<T>(y < H ? y : H - 1, sh, h);
+            wt.ly0[j] = ty.l0; wt.ly1[j] = ty.l1;
+            o00[j] = (ty.i0 - ty_lo) * stride + (tx.i0 - tx_lo);
+            o10[j] = (ty.i1 - ty_lo) * stride + (tx.i0 - tx_lo);
+            acc[j] = (T)0;
+            if (j == 0) a0 = ty.i0;
+            const int d = ty.i0 - a0;                                  // non-decreasing in j
+            regular = regular && d >= 0 && d <= (NPX == LR_PPT ? 1 : 3);       // what one pixel's field of the code holds
+            if constexpr (NPX != LR_PPT) pat |= (d & 3) << (2 * j);
+            else if (j > 0) pat |= (d & 1) << (j - 1);
+        }
+        dx1 = tx.i1 - tx.i0;
+        upat = __builtin_amdgcn_readfirstlane(regular ? pat : -1);       // the rows of a wave are shared by its lanes
+    }
+};
+
+// One channel chunk for any other geometry (factors below 3, rows clamped past the image): NPX independent pixels.
+// I is the caller's index width for ch * plane (int in the register-staged kernel, size_t in the DMA ones).
+template <typename I, typename T, int NPX>
+__device__ __forceinline__ void lr_generic_chunk(const T *tile, int cc, int plane, LrLane<T, NPX> &L)
+{
+#pragma unroll 1
+    for (int ch = 0; ch < cc; ++ch) {
+        const T *tp = tile + (I)ch * plane;
+#pragma unroll
+        for (int j = 0; j < NPX; ++j) {
+            const T v = bilerp<T>(tp[L.o00[j]], tp[L.o00[j] + L.dx1], tp[L.o10[j]], tp[L.o10[j] + L.dx1], L.wt.lx0, L.wt.lx1, L.wt.ly0[j], L.wt.ly1[j]);
+            L.acc[j] = fma_t(v, v, L.acc[j]);
+        }
+    }
+}
+
+// Radius of the lane's live pixels from their sums of squares, the store, and the block's min / max partial.
+template <int MODE, typename T, int NPX>
+__device__ __forceinline__ void lr_finish(const LrTile &t, const LrLane<T, NPX> &L, int H, int W, double ks, double rks,
+                                          T *__restrict__ out, double *__restrict__ partials)
+{
+    const int x = t.X0 + (int)(threadIdx.x & (LR_TW - 1)), ly = threadIdx.x / LR_TW;
+    double mn = 0.0, mx = 0.0;
+    bool have = false;
+#pragma unroll
+    for (int j = 0; j < NPX; ++j) {
+        if (!L.live[j]) continue;
+        const int y = t.Y0 + ly * NPX + j;
+        T r;
+        if constexpr (MODE == 0) r = dist0_from_ssq(L.acc[j], ks, rks);
+        else if constexpr (sizeof(T) == 8) r = __builtin_sqrt(L.acc[j]);
+        else r = __builtin_sqrtf(L.acc[j]);
+        out[(size_t)t.b * H * W + (size_t)y * W + x] = r;
+        if (!have) { mn = mx = (double)r; have = true; }
+        else { mn = nan_min(mn, (double)r); mx = nan_max(mx, (double)r); }
+    }
+    __shared__ double seed[2];
+    if (threadIdx.x == 0) { seed[0] = mn; seed[1] = mx; }         // thread 0 (pixel X0,Y0) is always live
+    __syncthreads();
+    if (!have) { mn = seed[0]; mx = seed[1]; }
+    block_minmax<TPB>(mn, mx, partials + (size_t)t.id * 2);
+}
+
 
 // One channel chunk of the window for a lane's LR_PPT vertically adjacent pixels, when their upper tap rows are
 // R + {0, PAT bit 0, PAT bit 1, PAT bit 2} (wave-uniform, compile-time): the lane reads the 2 or 3 source rows once per
@@ -1149,22 +1244,24 @@ template <typename T, int PAT> struct LrRows {
             if constexpr (PAT != 0) { v[2][0] = tp[2 * stride]; v[2][1] = tp[2 * stride + 1]; }
         }
     }
-    __device__ __forceinline__ void accumulate(const LrW<T> &wt, T (&acc)[LR_PPT]) const
-    {
-        // the column interpolation of each source row once, shared by the lane's pixels that read the row (2 or 3 rows for 4
-        // pixels: 16-18 float64 operations per channel where four independent pixels take 28)
-        T t[3];
-        t[0] = col_lerp(wt.lx0, wt.lx1, v[0][0], v[0][1]);
-        t[1] = col_lerp(wt.lx0, wt.lx1, v[1][0], v[1][1]);
-        if constexpr (PAT != 0) t[2] = col_lerp(wt.lx0, wt.lx1, v[2][0], v[2][1]);
-#pragma unroll
-        for (int j = 0; j < LR_PPT; ++j) {
-            const int a = j == 0 ? 0 : (PAT >> (j - 1)) & 1;      // 0 or 1; a + 1 == 2 only when PAT != 0
-            const T x = col_lerp(wt.ly0[j], wt.ly1[j], t[a], t[a + 1]);
-            acc[j] = fma_t(x, x, acc[j]);
-        }
-    }
 };
+// The row words v of one channel (LrRows or LrRowsImm) into the lane's LR_PPT accumulators.
+template <int PAT, typename T>
+__device__ __forceinline__ void lr_rows_accumulate(const T (&v)[3][2], const LrW<T> &wt, T (&acc)[LR_PPT])
+{
+    // the column interpolation of each source row once, shared by the lane's pixels that read the row (2 or 3 rows for 4
+    // pixels: 16-18 float64 operations per channel where four independent pixels take 28)
+    T t[3];
+    t[0] = col_lerp(wt.lx0, wt.lx1, v[0][0], v[0][1]);
+    t[1] = col_lerp(wt.lx0, wt.lx1, v[1][0], v[1][1]);
+    if constexpr (PAT != 0) t[2] = col_lerp(wt.lx0, wt.lx1, v[2][0], v[2][1]);
+#pragma unroll
+    for (int j = 0; j < LR_PPT; ++j) {
+        const int a = j == 0 ? 0 : (PAT >> (j - 1)) & 1;      // 0 or 1; a + 1 == 2 only when PAT != 0
+        const T x = col_lerp(wt.ly0[j], wt.ly1[j], t[a], t[a + 1]);
+        acc[j] = fma_t(x, x, acc[j]);
+    }
+}
 template <typename T, int PAT>
 __device__ __forceinline__ void lr_rows_chunk(const T *__restrict__ tp, int cc, int plane, int stride, const LrW<T> &wt, T (&acc)[LR_PPT])
 {
@@ -1172,7 +1269,7 @@ __device__ __forceinline__ void lr_rows_chunk(const T *__restrict__ tp, int cc, 
     for (int ch = 0; ch < cc; ++ch, tp += plane) {
         LrRows<T, PAT> A;
         A.load(tp, stride);
-        A.accumulate(wt, acc);
+        lr_rows_accumulate<PAT>(A.v, wt, acc);
     }
 }
 
@@ -1188,49 +1285,16 @@ __global__ void __launch_bounds__(TPB) k_feat_reduce_lr(const T *__restrict__ fe
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lr_smem[];
     T *tile = reinterpret_cast<T *>(lr_smem);                    // [CC][max_rows][max_cols]
-    // Tile <-> block: workgroups go to the 8 XCDs round-robin in launch order, each XCD with its own L2.  Tiles that are
-    // neighbours along x share the source lines at their common border (a tile's 19-element window rows straddle two
-    // 128-byte lines), so in launch order every line would be fetched by two XCDs.  Give the blocks that share an XCD
-    // (id % 8) one contiguous eighth of the row-major tile list instead -- bijective for any tile count.
-    const unsigned ntx = gridDim.x, nty = gridDim.y, ntiles = ntx * nty * gridDim.z;
-    const unsigned lin = blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z);
-    const unsigned xq = ntiles / 8, xr = ntiles % 8, xk = lin % 8;
-    const unsigned tile_id = (xk < xr ? xk * (xq + 1) : xr * (xq + 1) + (xk - xr) * xq) + lin / 8;
-    const int bx = (int)(tile_id % ntx), by = (int)((tile_id / ntx) % nty);
-    const int b = (int)(tile_id / (ntx * nty));
-    const int X0 = bx * LR_TW, Y0 = by * LR_TH;
-    const int lx = threadIdx.x & (LR_TW - 1), ly = threadIdx.x / LR_TW;      // ly = wave in 0..3
-    const int x = X0 + lx;
+    const LrTile t = lr_tile<LR_TH>();
+    const int X0 = t.X0, Y0 = t.Y0;
     // tap window of this block in the low-res grid
     const int ylast = (Y0 + LR_TH - 1 < H ? Y0 + LR_TH - 1 : H - 1), xlast = (X0 + LR_TW - 1 < W ? X0 + LR_TW - 1 : W - 1);
     const int ty_lo = make_taps<T>(Y0, sh, h).i0, ty_hi = make_taps<T>(ylast, sh, h).i1;
     const int tx_lo = make_taps<T>(X0, sw, w).i0, tx_hi = make_taps<T>(xlast, sw, w).i1;
     const int rows = ty_hi - ty_lo + 2, cols = tx_hi - tx_lo + 2;            // with the extra row / column; <= max_rows / max_cols
-    const bool xin = x < W;
-    const Taps<T> tx = make_taps<T>(xin ? x : W - 1, sw, w);
-    T acc[LR_PPT];
-    LrW<T> wt;
-    wt.lx0 = tx.l0; wt.lx1 = tx.l1;
-    int o00[LR_PPT], o10[LR_PPT];
-    bool live[LR_PPT];
-    int a0 = 0, pat = 0;
-    bool regular = true;         // wave-uniform: the rows' upper taps are R + {0, 1}
-#pragma unroll
-    for (int j = 0; j < LR_PPT; ++j) {
-        const int y = Y0 + ly * LR_PPT + j;
-        live[j] = xin && y < H;
-        const Taps<T> ty = make_taps<T>(y < H ? y : H - 1, sh, h);
-        wt.ly0[j] = ty.l0; wt.ly1[j] = ty.l1;
-        o00[j] = (ty.i0 - ty_lo) * max_cols + (tx.i0 - tx_lo);
-        o10[j] = (ty.i1 - ty_lo) * max_cols + (tx.i0 - tx_lo);
-        acc[j] = (T)0;
-        if (j == 0) a0 = ty.i0;
-        const int d = ty.i0 - a0;                                  // non-decreasing in j
-        regular = regular && (d == 0 || d == 1);
-        if (j > 0) pat |= (d & 1) << (j - 1);
-    }
-    const int dx1 = tx.i1 - tx.i0;
-    const T *fb = feat + (size_t)b * bstride;
+    LrLane<T> L;
+    L.setup(t, H, W, sh, sw, h, w, ty_lo, tx_lo, max_cols);
+    const T *fb = feat + (size_t)t.b * bstride;
     const int plane = max_rows * max_cols;
     // staging offsets of this lane inside one channel plane of the window
     int st_src[LR_STAGE_IT], st_dst[LR_STAGE_IT];
@@ -1244,7 +1308,6 @@ __global__ void __launch_bounds__(TPB) k_feat_reduce_lr(const T *__restrict__ fe
         st_src[it] = sr * w + sq;
         st_dst[it] = r * max_cols + q;
     }
-    const int upat = __builtin_amdgcn_readfirstlane(regular ? pat : -1);       // the rows of a wave are shared by its lanes
     // Staging: wave k of the block owns channels k, k + 4, ... of a chunk (CC <= 4 * LR_STAGE_G, so at most LR_STAGE_G
     // of them), its lanes walk the window with precomputed offsets; all loads are issued before the first LDS write so
     // that the chunk costs one memory round trip.  (Issuing the loads of chunk n + 1 before the arithmetic of chunk n
@@ -1279,43 +1342,14 @@ __global__ void __launch_bounds__(TPB) k_feat_reduce_lr(const T *__restrict__ fe
             }
         }
         __syncthreads();
-        const T *t0 = tile + o00[0];
-        if (upat == 0) lr_rows_chunk<T, 0>(t0, cc, plane, max_cols, wt, acc);
-        else if (upat == 4) lr_rows_chunk<T, 4>(t0, cc, plane, max_cols, wt, acc);
-        else if (upat == 6) lr_rows_chunk<T, 6>(t0, cc, plane, max_cols, wt, acc);
-        else if (upat == 7) lr_rows_chunk<T, 7>(t0, cc, plane, max_cols, wt, acc);
-        else {
-            // any other geometry (factors below 3, rows clamped past the image): four independent pixels
-#pragma unroll 1
-            for (int ch = 0; ch < cc; ++ch) {
-                const T *tp = tile + ch * plane;
-#pragma unroll
-                for (int j = 0; j < LR_PPT; ++j) {
-                    const T v = bilerp<T>(tp[o00[j]], tp[o00[j] + dx1], tp[o10[j]], tp[o10[j] + dx1], wt.lx0, wt.lx1, wt.ly0[j], wt.ly1[j]);
-                    acc[j] = fma_t(v, v, acc[j]);
-                }
-            }
-        }
+        const T *t0 = tile + L.o00[0];
+        if (L.upat == 0) lr_rows_chunk<T, 0>(t0, cc, plane, max_cols, L.wt, L.acc);
+        else if (L.upat == 4) lr_rows_chunk<T, 4>(t0, cc, plane, max_cols, L.wt, L.acc);
+        else if (L.upat == 6) lr_rows_chunk<T, 6>(t0, cc, plane, max_cols, L.wt, L.acc);
+        else if (L.upat == 7) lr_rows_chunk<T, 7>(t0, cc, plane, max_cols, L.wt, L.acc);
+        else lr_generic_chunk<int>(tile, cc, plane, L);
     }
-    double mn = 0.0, mx = 0.0;
-    bool have = false;
-#pragma unroll
-    for (int j = 0; j < LR_PPT; ++j) {
-        if (!live[j]) continue;
-        const int y = Y0 + ly * LR_PPT + j;
-        T r;
-        if constexpr (MODE == 0) r = dist0_from_ssq(acc[j], ks, rks);
-        else if constexpr (sizeof(T) == 8) r = __builtin_sqrt(acc[j]);
-        else r = __builtin_sqrtf(acc[j]);
-        out[(size_t)b * H * W + (size_t)y * W + x] = r;
-        if (!have) { mn = mx = (double)r; have = true; }
-        else { mn = nan_min(mn, (double)r); mx = nan_max(mx, (double)r); }
-    }
-    __shared__ double seed[2];
-    if (threadIdx.x == 0) { seed[0] = mn; seed[1] = mx; }         // thread 0 (pixel X0,Y0) is always live
-    __syncthreads();
-    if (!have) { mn = seed[0]; mx = seed[1]; }
-    block_minmax<TPB>(mn, mx, partials + (size_t)tile_id * 2);
+    lr_finish<MODE>(t, L, H, W, ks, rks, out, partials);
 }
 
 // ---- k_feat_reduce_lr with the window staged by LDS-DMA into a double buffer (float64, even source width).
@@ -1353,48 +1387,17 @@ __global__ void __launch_bounds__(TPB) k_feat_reduce_lr_dma(const double *__rest
     T *img = reinterpret_cast<T *>(lr_smem);                     // two images of DMA_UNITS * 2 doubles
     typedef __attribute__((address_space(3))) unsigned char *lds_bytes;
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_bytes)lr_smem;
-    // tile <-> block: XCD-contiguous eighths of the row-major tile list (see k_feat_reduce_lr)
-    const unsigned ntx = gridDim.x, nty = gridDim.y, ntiles = ntx * nty * gridDim.z;
-    const unsigned lin = blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z);
-    const unsigned xq = ntiles / 8, xr = ntiles % 8, xk = lin % 8;
-    const unsigned tile_id = (xk < xr ? xk * (xq + 1) : xr * (xq + 1) + (xk - xr) * xq) + lin / 8;
-    const int bx = (int)(tile_id % ntx), by = (int)((tile_id / ntx) % nty);
-    const int b = (int)(tile_id / (ntx * nty));
-    const int X0 = bx * LR_TW, Y0 = by * LR_TH;
-    const int lx = threadIdx.x & (LR_TW - 1), ly = threadIdx.x / LR_TW;      // ly = wave in 0..3
+    const LrTile t = lr_tile<LR_TH>();
+    const int X0 = t.X0, Y0 = t.Y0;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int x = X0 + lx;
     const int ylast = (Y0 + LR_TH - 1 < H ? Y0 + LR_TH - 1 : H - 1), xlast = (X0 + LR_TW - 1 < W ? X0 + LR_TW - 1 : W - 1);
     const int ty_lo = make_taps<T>(Y0, sh, h).i0, ty_hi = make_taps<T>(ylast, sh, h).i1;
     const int tx_lo = make_taps<T>(X0, sw, w).i0 & ~1, tx_hi = make_taps<T>(xlast, sw, w).i1;       // even start column
     const int rows = ty_hi - ty_lo + 2;                          // with the clamped extra row
     const int U = (tx_hi - tx_lo + 2 + 1) >> 1;                  // pairs per row, covering the clamped extra column
     const int per = rows * U, stride = 2 * U, plane = 2 * per;   // units per channel; row / channel strides in doubles
-    const bool xin = x < W;
-    const Taps<T> tx = make_taps<T>(xin ? x : W - 1, sw, w);
-    T acc[LR_PPT];
-    LrW<T> wt;
-    wt.lx0 = tx.l0; wt.lx1 = tx.l1;
-    int o00[LR_PPT], o10[LR_PPT];
-    bool live[LR_PPT];
-    int a0 = 0, pat = 0;
-    bool regular = true;
-#pragma unroll
-    for (int j = 0; j < LR_PPT; ++j) {
-        const int y = Y0 + ly * LR_PPT + j;
-        live[j] = xin && y < H;
-        const Taps<T> ty = make_taps<T>(y < H ? y : H - 1, sh, h);
-        wt.ly0[j] = ty.l0; wt.ly1[j] = ty.l1;
-        o00[j] = (ty.i0 - ty_lo) * stride + (tx.i0 - tx_lo);
-        o10[j] = (ty.i1 - ty_lo) * stride + (tx.i0 - tx_lo);
-        acc[j] = (T)0;
-        if (j == 0) a0 = ty.i0;
-        const int d = ty.i0 - a0;
-        regular = regular && (d == 0 || d == 1);
-        if (j > 0) pat |= (d & 1) << (j - 1);
-    }
-    const int dx1 = tx.i1 - tx.i0;
-    const int upat = __builtin_amdgcn_readfirstlane(regular ? pat : -1);
+    LrLane<T> L;
+    L.setup(t, H, W, sh, sw, h, w, ty_lo, tx_lo, stride);
     // this lane's DMA_PER_WAVE units of a chunk: source offset (doubles, from the chunk's first plane) and channel inside the chunk
     const long long hwl = (long long)h * w;
     unsigned soff[DMA_PER_WAVE], sch[DMA_PER_WAVE];
@@ -1408,7 +1411,7 @@ __global__ void __launch_bounds__(TPB) k_feat_reduce_lr_dma(const double *__rest
         sch[i] = (unsigned)ch;
         soff[i] = (unsigned)(sr * w + q0);
     }
-    const T *fb = feat + (size_t)b * bstride;
+    const T *fb = feat + (size_t)t.b * bstride;
     auto issue = [&](int c0, int buf) {
         const int cc = C - c0 < CC ? C - c0 : CC;
 #pragma unroll
@@ -1441,43 +1444,29 @@ __global__ void __launch_bounds__(TPB) k_feat_reduce_lr_dma(const double *__rest
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        const T *t0 = tile + o00[0];
-        if (upat == 0) lr_rows_chunk<T, 0>(t0, cc, plane, stride, wt, acc);
-        else if (upat == 4) lr_rows_chunk<T, 4>(t0, cc, plane, stride, wt, acc);
-        else if (upat == 6) lr_rows_chunk<T, 6>(t0, cc, plane, stride, wt, acc);
-        else if (upat == 7) lr_rows_chunk<T, 7>(t0, cc, plane, stride, wt, acc);
+        const T *t0 = tile + L.o00[0];
+        if (L.upat == 0) lr_rows_chunk<T, 0>(t0, cc, plane, stride, L.wt, L.acc);
+        else if (L.upat == 4) lr_rows_chunk<T, 4>(t0, cc, plane, stride, L.wt, L.acc);
+        else if (L.upat == 6) lr_rows_chunk<T, 6>(t0, cc, plane, stride, L.wt, L.acc);
+        else if (L.upat == 7) lr_rows_chunk<T, 7>(t0, cc, plane, stride, L.wt, L.acc);
         else {
+            // lr_generic_chunk<size_t>, written out: called as a function, however its arguments are passed, the loop comes back
+            // from the compiler with one address register per tap stepped per channel (16 more live VGPRs) where this form steps
+            // one scalar base, and the kernel takes 126 VGPRs instead of 94 -- 4 waves per SIMD instead of 5
 #pragma unroll 1
             for (int ch = 0; ch < cc; ++ch) {
                 const T *tp = tile + (size_t)ch * plane;
 #pragma unroll
                 for (int j = 0; j < LR_PPT; ++j) {
-                    const T v = bilerp<T>(tp[o00[j]], tp[o00[j] + dx1], tp[o10[j]], tp[o10[j] + dx1], wt.lx0, wt.lx1, wt.ly0[j], wt.ly1[j]);
-                    acc[j] = fma_t(v, v, acc[j]);
+                    const T v = bilerp<T>(tp[L.o00[j]], tp[L.o00[j] + L.dx1], tp[L.o10[j]], tp[L.o10[j] + L.dx1], L.wt.lx0, L.wt.lx1, L.wt.ly0[j], L.wt.ly1[j]);
+                    L.acc[j] = fma_t(v, v, L.acc[j]);
                 }
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this wave's reads of the image are retired ...
         __builtin_amdgcn_s_barrier();                             // ... and everybody's, before the next iteration restages it
     }
-    double mn = 0.0, mx = 0.0;
-    bool have = false;
-#pragma unroll
-    for (int j = 0; j < LR_PPT; ++j) {
-        if (!live[j]) continue;
-        const int y = Y0 + ly * LR_PPT + j;
-        T r;
-        if constexpr (MODE == 0) r = dist0_from_ssq(acc[j], ks, rks);
-        else r = __builtin_sqrt(acc[j]);
-        out[(size_t)b * H * W + (size_t)y * W + x] = r;
-        if (!have) { mn = mx = (double)r; have = true; }
-        else { mn = nan_min(mn, (double)r); mx = nan_max(mx, (double)r); }
-    }
-    __shared__ double seed[2];
-    if (threadIdx.x == 0) { seed[0] = mn; seed[1] = mx; }         // thread 0 (pixel X0,Y0) is always live
-    __syncthreads();
-    if (!have) { mn = seed[0]; mx = seed[1]; }
-    block_minmax<TPB>(mn, mx, partials + (size_t)tile_id * 2);
+    lr_finish<MODE>(t, L, H, W, ks, rks, out, partials);
 }
 
 // ---- k_feat_reduce_lr_dma with a COMPILE-TIME image geometry: ROWS x UU pairs per channel, CCF = DMA_UNITS / (ROWS * UU)
@@ -1513,21 +1502,6 @@ template <int PAT, int OFF, int STRIDE_B> struct LrRowsImm {
         else
             asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(v[0][0]), "+v"(v[0][1]), "+v"(v[1][0]), "+v"(v[1][1]) : "n"(N) : "memory");
     }
-    __device__ __forceinline__ void accumulate(const LrW<double> &wt, double (&acc)[LR_PPT]) const
-    {
-        // the column interpolation of each source row once, shared by the lane's pixels that read the row (2 or 3 rows for 4
-        // pixels: 16-18 float64 operations per channel where four independent pixels take 28)
-        double t[3];
-        t[0] = col_lerp(wt.lx0, wt.lx1, v[0][0], v[0][1]);
-        t[1] = col_lerp(wt.lx0, wt.lx1, v[1][0], v[1][1]);
-        if constexpr (PAT != 0) t[2] = col_lerp(wt.lx0, wt.lx1, v[2][0], v[2][1]);
-#pragma unroll
-        for (int j = 0; j < LR_PPT; ++j) {
-            const int a = j == 0 ? 0 : (PAT >> (j - 1)) & 1;
-            const double x = col_lerp(wt.ly0[j], wt.ly1[j], t[a], t[a + 1]);
-            acc[j] = fma_t(x, x, acc[j]);
-        }
-    }
 };
 
 template <int PAT, int ROWS, int UU, int CH, int CCF, bool FULL>
@@ -1539,11 +1513,11 @@ __device__ __forceinline__ void lr_imm_steps(unsigned base, int cc, LrRowsImm<PA
         LrRowsImm<PAT, ((CH + 1) % CCF) * ROWS * UU * 16, UU * 16> nxt;
         nxt.issue(base);                                   // channel CH + 1 on its way ...
         cur.template wait<NREAD>();                        // ... channel CH has landed
-        if (FULL || CH < cc) cur.accumulate(wt, acc);
+        if (FULL || CH < cc) lr_rows_accumulate<PAT>(cur.v, wt, acc);
         lr_imm_steps<PAT, ROWS, UU, CH + 1, CCF, FULL>(base, cc, nxt, wt, acc);
     } else {
         cur.template wait<0>();
-        if (FULL || CH < cc) cur.accumulate(wt, acc);
+        if (FULL || CH < cc) lr_rows_accumulate<PAT>(cur.v, wt, acc);
     }
 }
 
@@ -1660,49 +1634,14 @@ __global__ void __launch_bounds__(TPB, (PPT > LR_PPT ? HALO_LR8_WAVES : 1)) k_fe
     T *img = reinterpret_cast<T *>(lr_smem);
     typedef __attribute__((address_space(3))) unsigned char *lds_bytes;
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_bytes)lr_smem;
-    const unsigned ntx = gridDim.x, nty = gridDim.y, ntiles = ntx * nty * gridDim.z;
-    const unsigned lin = blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z);
-    const unsigned xq = ntiles / 8, xr = ntiles % 8, xk = lin % 8;
-    const unsigned tile_id = (xk < xr ? xk * (xq + 1) : xr * (xq + 1) + (xk - xr) * xq) + lin / 8;
-    const int bx = (int)(tile_id % ntx), by = (int)((tile_id / ntx) % nty);
-    const int b = (int)(tile_id / (ntx * nty));
-    const int X0 = bx * LR_TW, Y0 = by * TH;
-    const int lx = threadIdx.x & (LR_TW - 1), ly = threadIdx.x / LR_TW;
+    const LrTile t = lr_tile<TH>();
+    const int X0 = t.X0, Y0 = t.Y0;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int x = X0 + lx;
     const int xlast = (X0 + LR_TW - 1 < W ? X0 + LR_TW - 1 : W - 1);
     const int ty_lo = make_taps<T>(Y0, sh, h).i0;
     const int tx_lo = make_taps<T>(X0, sw, w).i0 & ~1, tx_hi = make_taps<T>(xlast, sw, w).i1;
-    const bool xin = x < W;
-    const Taps<T> tx = make_taps<T>(xin ? x : W - 1, sw, w);
-    T acc[PPT];
-    LrW<T, PPT> wt;
-    wt.lx0 = tx.l0; wt.lx1 = tx.l1;
-    int o00[PPT], o10[PPT];
-    bool live[PPT];
-    int a0 = 0, pat = 0;
-    bool regular = true;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const int y = Y0 + ly * PPT + j;
-        live[j] = xin && y < H;
-        const Taps<T> ty = make_taps<T>(y < H ? y : H - 1, sh, h);
-        wt.ly0[j] = ty.l0; wt.ly1[j] = ty.l1;
-        o00[j] = (ty.i0 - ty_lo) * STRIDE + (tx.i0 - tx_lo);
-        o10[j] = (ty.i1 - ty_lo) * STRIDE + (tx.i0 - tx_lo);
-        acc[j] = (T)0;
-        if (j == 0) a0 = ty.i0;
-        const int d = ty.i0 - a0;
-        if constexpr (PPT == LR_PPT) {
-            regular = regular && (d == 0 || d == 1);
-            if (j > 0) pat |= (d & 1) << (j - 1);
-        } else {                                                    // 2 bits per pixel: LrRowsImmN's row code
-            regular = regular && d >= 0 && d <= 3;
-            pat |= (d & 3) << (2 * j);
-        }
-    }
-    const int dx1 = tx.i1 - tx.i0;
-    const int upat = __builtin_amdgcn_readfirstlane(regular ? pat : -1);
+    LrLane<T, PPT> L;
+    L.setup(t, H, W, sh, sw, h, w, ty_lo, tx_lo, STRIDE);
     const long long hwl = (long long)h * w;
     unsigned soff[DMA_PER_WAVE], sch[DMA_PER_WAVE];
 #pragma unroll
@@ -1718,7 +1657,7 @@ __global__ void __launch_bounds__(TPB, (PPT > LR_PPT ? HALO_LR8_WAVES : 1)) k_fe
         sch[i] = (unsigned)(ch < CCF ? ch : CCF - 1);
         soff[i] = (unsigned)(sr * w + q0);
     }
-    const T *fb = feat + (size_t)b * bstride;
+    const T *fb = feat + (size_t)t.b * bstride;
     // per-lane source pointers of the chunk to be issued next, advanced by CCF planes per chunk (two VALU instructions per
     // pointer and chunk instead of re-deriving channel * plane + offset); the last, partial chunk clamps its channel
     const T *sp[DMA_PER_WAVE];
@@ -1769,55 +1708,28 @@ __global__ void __launch_bounds__(TPB, (PPT > LR_PPT ? HALO_LR8_WAVES : 1)) k_fe
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        const unsigned base = lds0 + (unsigned)(n & 1) * (DMA_UNITS * 16) + (unsigned)o00[0] * 8u;
+        const unsigned base = lds0 + (unsigned)(n & 1) * (DMA_UNITS * 16) + (unsigned)L.o00[0] * 8u;
         bool done = false;
         if constexpr (PPT == LR_PPT) {
             done = true;
-            if (upat == 0) lr_imm_chunk<0, ROWS, UU, CCF>(base, cc, wt, acc);
-            else if (upat == 4) lr_imm_chunk<4, ROWS, UU, CCF>(base, cc, wt, acc);
-            else if (upat == 6) lr_imm_chunk<6, ROWS, UU, CCF>(base, cc, wt, acc);
-            else if (upat == 7) lr_imm_chunk<7, ROWS, UU, CCF>(base, cc, wt, acc);
+            if (L.upat == 0) lr_imm_chunk<0, ROWS, UU, CCF>(base, cc, L.wt, L.acc);
+            else if (L.upat == 4) lr_imm_chunk<4, ROWS, UU, CCF>(base, cc, L.wt, L.acc);
+            else if (L.upat == 6) lr_imm_chunk<6, ROWS, UU, CCF>(base, cc, L.wt, L.acc);
+            else if (L.upat == 7) lr_imm_chunk<7, ROWS, UU, CCF>(base, cc, L.wt, L.acc);
             else done = false;
         } else {
-            switch (upat) {
-#define HALO_LR_CASE(CODE_) case (int)CODE_: lr_immn_chunk<PPT, CODE_, ROWS, UU, CCF>(base, cc, wt, acc); done = true; break;
+            switch (L.upat) {
+#define HALO_LR_CASE(CODE_) case (int)CODE_: lr_immn_chunk<PPT, CODE_, ROWS, UU, CCF>(base, cc, L.wt, L.acc); done = true; break;
                 HALO_LR_CODES8(HALO_LR_CASE)
 #undef HALO_LR_CASE
                 default: break;
             }
         }
-        if (!done) {
-#pragma unroll 1
-            for (int ch = 0; ch < cc; ++ch) {
-                const T *tp = tile + (size_t)ch * PLANE;
-#pragma unroll
-                for (int j = 0; j < PPT; ++j) {
-                    const T v = bilerp<T>(tp[o00[j]], tp[o00[j] + dx1], tp[o10[j]], tp[o10[j] + dx1], wt.lx0, wt.lx1, wt.ly0[j], wt.ly1[j]);
-                    acc[j] = fma_t(v, v, acc[j]);
-                }
-            }
-        }
+        if (!done) lr_generic_chunk<size_t>(tile, cc, PLANE, L);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
-    double mn = 0.0, mx = 0.0;
-    bool have = false;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        if (!live[j]) continue;
-        const int y = Y0 + ly * PPT + j;
-        T r;
-        if constexpr (MODE == 0) r = dist0_from_ssq(acc[j], ks, rks);
-        else r = __builtin_sqrt(acc[j]);
-        out[(size_t)b * H * W + (size_t)y * W + x] = r;
-        if (!have) { mn = mx = (double)r; have = true; }
-        else { mn = nan_min(mn, (double)r); mx = nan_max(mx, (double)r); }
-    }
-    __shared__ double seed[2];
-    if (threadIdx.x == 0) { seed[0] = mn; seed[1] = mx; }
-    __syncthreads();
-    if (!have) { mn = seed[0]; mx = seed[1]; }
-    block_minmax<TPB>(mn, mx, partials + (size_t)tile_id * 2);
+    lr_finish<MODE>(t, L, H, W, ks, rks, out, partials);
 }
 
 // ---- Gram form of the low-resolution radius ("precompute the 4-neighbour Gram terms per low-res cell,
@@ -2228,6 +2140,11 @@ static int launch_feat_lr(const halo_score_args &a, ScorePlan &p, T *out, hipStr
     const T sh = H > 1 ? (T)(hf - 1) / (T)(H - 1) : (T)0, sw = W > 1 ? (T)(wf - 1) / (T)(W - 1) : (T)0;
     dim3 grid((unsigned)cdiv(W, LR_TW), (unsigned)cdiv(H, LR_TH), (unsigned)B), block(TPB);
     nblk = (int)(grid.x * grid.y);
+    // MODE (0: radius, 1: Euclidean norm) is a template parameter of every kernel below: chosen here, each launch is written once
+    auto with_mode = [mode](auto launch) {
+        if (mode == 0) launch(std::integral_constant<int, 0>());
+        else launch(std::integral_constant<int, 1>());
+    };
     if constexpr (sizeof(T) == 8) {
         // LDS-DMA double buffer (k_feat_reduce_lr_dma): float64, even source width (16-byte aligned pairs), at least 4 channels
         // of the largest window per 16 KiB image; otherwise the register-staged kernel (same bits)
@@ -2249,9 +2166,9 @@ static int launch_feat_lr(const halo_score_args &a, ScorePlan &p, T *out, hipStr
 #define HALO_LR_FIXED8(R_, U_)                                                                                                             \
                 if (max_rows8 <= R_ && need_u <= U_) {                                                                                     \
                     nblk = (int)(grid8.x * grid8.y);                                                                                       \
-                    if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
-                    else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
-                    return HALO_OK;                                                                                                        \
+                    with_mode([&](auto M) { hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<decltype(M)::value, R_, U_, 2 * LR_PPT>), grid8, block, lds, st, \
+                                                               (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); }); \
+                    return HALO_OK;                                                                                                       \
                 }
                 HALO_LR_FIXED8(8, 8)       // x6.4 (160x320 -> 1024x2048): 16 channels per image
                 HALO_LR_FIXED8(11, 10)     // x4: 9 channels per image
@@ -2259,16 +2176,16 @@ static int launch_feat_lr(const halo_score_args &a, ScorePlan &p, T *out, hipStr
             }
 #define HALO_LR_FIXED(R_, U_)                                                                                                              \
             if (need_rows <= R_ && need_u <= U_) {                                                                                         \
-                if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<0, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); \
-                else hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<1, R_, U_>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials);           \
+                with_mode([&](auto M) { hipLaunchKernelGGL((k_feat_reduce_lr_dmaf<decltype(M)::value, R_, U_>), grid, block, lds, st,      \
+                                                           (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, ks, rks, (double *)out, partials); }); \
                 return HALO_OK;                                                                                                            \
             }
             HALO_LR_FIXED(6, 8)        // x6.4 (160x320 -> 1024x2048): 21 channels per image
             HALO_LR_FIXED(7, 10)       // x4: 14 channels per image
             HALO_LR_FIXED(8, 12)
 #undef HALO_LR_FIXED
-            if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr_dma<0>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials);
-            else hipLaunchKernelGGL((k_feat_reduce_lr_dma<1>), grid, block, lds, st, (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials);
+            with_mode([&](auto M) { hipLaunchKernelGGL((k_feat_reduce_lr_dma<decltype(M)::value>), grid, block, lds, st,
+                                                       (const double *)feat, bstride, C, hf, wf, H, W, (double)sh, (double)sw, CCd, ks, rks, (double *)out, partials); });
             return HALO_OK;
         }
     }
@@ -2279,8 +2196,8 @@ static int launch_feat_lr(const halo_score_args &a, ScorePlan &p, T *out, hipStr
     CC = CC > (TPB / 64) * LR_STAGE_G ? (TPB / 64) * LR_STAGE_G : CC;
     CC = CC > C ? C : CC;
     const size_t lds = (size_t)CC * plane_bytes;
-    if (mode == 0) hipLaunchKernelGGL((k_feat_reduce_lr<T, 0>), grid, block, lds, st, feat, bstride, C, hf, wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials);
-    else hipLaunchKernelGGL((k_feat_reduce_lr<T, 1>), grid, block, lds, st, feat, bstride, C, hf, wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials);
+    with_mode([&](auto M) { hipLaunchKernelGGL((k_feat_reduce_lr<T, decltype(M)::value>), grid, block, lds, st,
+                                               feat, bstride, C, hf, wf, H, W, sh, sw, max_rows, max_cols, CC, ks, rks, out, partials); });
     return HALO_OK;
 }
 

@@ -1277,6 +1277,28 @@ def test_lowres_sources_f32_embedding_and_other_class_counts(dev):
             assert bits_equal(x.cpu().numpy(), y.cpu().numpy())
 
 
+@pytest.mark.parametrize("emb", ["float32", "float64", "float64_offset"])
+def test_lowres_euc_norm_through_the_register_staged_kernel(dev, emb):
+    """euc_norm (the kernels' MODE 1) through k_feat_reduce_lr, whose epilogue is the one all three low-res feature kernels share:
+    the float32 instantiation (sqrtf) and the float64 one, which only an embedding off 16-byte alignment reaches; the aligned
+    float64 embedding takes the LDS-DMA kernel with the same epilogue.  Ragged tiles in both directions (60 x 92 output)."""
+    from halo_amd.core.active.floating_region import score_maps, score_maps_lowres
+    from halo_amd.core.utils.hyperbolic import bilinear_align_corners
+    rng = np.random.default_rng(31)
+    lg = t(rng.standard_normal((1, 19, 20, 30)).astype(np.float32), dev)
+    em = t(rng.standard_normal((1, 10, 12, 18)) * 0.2, dev)
+    if emb == "float32":
+        em = em.float()
+    elif emb == "float64_offset":
+        em = _offset_copy(em)
+        assert em.data_ptr() % 16 != 0
+    a = score_maps_lowres(lg, em, (60, 92), "entropy", "euc_norm", True, None, ksize=3, mode="exact")
+    b = score_maps(bilinear_align_corners(lg, (60, 92)), bilinear_align_corners(em, (60, 92)), "entropy", "euc_norm", True, None, size=3)
+    assert a[1].dtype == em.dtype
+    for x, y in zip(a, b):
+        assert bits_equal(x.cpu().numpy(), y.cpu().numpy())
+
+
 def test_lowres_downsampling_falls_back_to_explicit_upsample(dev):
     """A source far larger than the target does not fit the LDS window: HaloUnsupported -> explicit path."""
     from halo_amd._lib import HaloUnsupported
