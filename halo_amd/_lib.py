@@ -95,6 +95,10 @@ SIGNATURES = {
     "halo_upcat_dwconv3x3_affine_relu_bwd_weight": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
     "halo_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "halo_pool_fold_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "halo_pool_fold_table": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "halo_pool_fold_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "halo_pool_fold_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
     "halo_event_create": (_vp, []),
     "halo_event_record": (_int, [_vp, _vp]),
     "halo_event_elapsed_ms": (_int, [_vp, _vp, C.POINTER(C.c_float)]),
@@ -112,7 +116,7 @@ SIGNATURES = {
 
 # must equal HALO_ABI_VERSION of include/halo_hip.h; bumped whenever an exported signature changes, so a stale
 # library with the same symbol names but older argument lists is refused instead of being called with shifted arguments
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lock = threading.Lock()
 _handle = None

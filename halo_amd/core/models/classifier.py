@@ -99,7 +99,36 @@ def broadcast_or_resize(pooled, size, resize):
     return resize(pooled, size)
 
 
-def v3plus_decoder(self, pyramid, low, resize):
+def folded_pooling(self, pooled):
+    """whether this head hands the pooled map to the bottleneck stage as it is: its class is marked by
+    halo_amd.hooks.use_folded_image_pooling and the map is 1 x 1 (the broadcast that a marked head leaves out is exact only then)"""
+    return getattr(type(self), "_halo_folded_image_pooling", False) and pooled.dim() == 4 and tuple(pooled.shape[2:]) == (1, 1)
+
+
+def pyramid_with_pooled(self, pyramid, pooled, size, resize):
+    """today's statements for the pooled branch: resized (or, under use_device_resize, broadcast) to the map and appended"""
+    if resize is None:
+        return pyramid + [F.interpolate(pooled, size=size, mode="bilinear", align_corners=True)]
+    return pyramid + [broadcast_or_resize(pooled, size, resize)]
+
+
+def v3plus_bottleneck(self, pyramid, pooled, resize):
+    """The bottleneck of a head marked by halo_amd.hooks.use_folded_image_pooling: pyramid holds the parallel branches alone, pooled
+    is global_branch's (B, Cg, 1, 1) output.  A `bottleneck` of the form Sequential(Conv2d, FrozenBatchNorm2d, nn.ReLU) inside the
+    operator's envelope (halo_amd.aspp.pool_fold_fallback_reason) runs halo_amd.aspp.pooled_bottleneck's operator, which reads
+    bottleneck[1]'s buffers itself (so fuse_norm_relu_pairs on the same head changes nothing here); anything else runs the
+    statements of an unmarked head -- over the branches' concatenation when the envelope, which looks at it, has already made it."""
+    from ... import aspp
+    bt = self.bottleneck
+    if isinstance(bt, nn.Sequential) and len(bt) == 3 and type(bt[2]) is nn.ReLU:
+        p = torch.cat(pyramid, dim=1)
+        if aspp.pool_fold_fallback_reason(p, pooled, bt[0], bt[1], bt[2]) is None:
+            return aspp.fused_pooled_bottleneck(p, pooled, bt[0], bt[1])
+        pyramid = [p]                            # outside the envelope: the concatenation made above is kept, the pooled map joins it
+    return self.bottleneck(torch.cat(pyramid_with_pooled(self, pyramid, pooled, pyramid[0].shape[2:], resize), dim=1))
+
+
+def v3plus_decoder(self, pyramid, low, resize, pooled=None):
     """The v3+ heads from the ASPP pyramid to the decoder's output (classifier.py:520-527): bottleneck, resize to the low-level
     map, concat with the shortcut, decoder.  Both package forwards call it.
 
@@ -109,13 +138,21 @@ def v3plus_decoder(self, pyramid, low, resize):
     decoder[0] is a depthwise-separable block (the six DepthwiseSeparableConv2d attributes, an nn.ReLU depthwise_activate) inside
     the operator's envelope (upcat_fallback_reason); any other marked instance, and every unmarked class, runs the statements
     below.  A marked head returns what the same head returns under use_device_resize + use_fused_depthwise on that block, bit for
-    bit; that is not bit-equal to the stock F.interpolate / nn.Conv2d chain."""
+    bit; that is not bit-equal to the stock F.interpolate / nn.Conv2d chain.
+
+    pooled: None, or -- from a head marked by halo_amd.hooks.use_folded_image_pooling -- global_branch's 1 x 1 output, which pyramid
+    then does not hold: the bottleneck runs as v3plus_bottleneck."""
+    def bottleneck():                            # the one place that says how the bottleneck's output is made
+        if pooled is None:
+            return self.bottleneck(torch.cat(pyramid, dim=1))
+        return v3plus_bottleneck(self, pyramid, pooled, resize)
+
     if getattr(type(self), "_halo_fused_decoder_front", False):
         from ...dwconv import upcat_fallback_reason, upsample_cat_depthwise_bn_relu
         from ...hooks import _DWSEP_ATTRS
         block = self.decoder[0] if isinstance(self.decoder, nn.Sequential) and len(self.decoder) > 0 else None
         if block is not None and all(hasattr(block, a) for a in _DWSEP_ATTRS) and type(block.depthwise_activate) is nn.ReLU:
-            top = self.bottleneck(torch.cat(pyramid, dim=1))
+            top = bottleneck()
             short = self.shortcut(low)
             if upcat_fallback_reason(top, short, block.depthwise_conv, block.depthwise_bn) is None:
                 dec = upsample_cat_depthwise_bn_relu(top, short, block.depthwise_conv, block.depthwise_bn)
@@ -129,10 +166,10 @@ def v3plus_decoder(self, pyramid, low, resize):
                 fused = resize(top, low.shape[2:])
             return self.decoder(torch.cat([fused, short], dim=1))
     if resize is None:
-        fused = self.bottleneck(torch.cat(pyramid, dim=1))
+        fused = bottleneck()
         fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
     else:
-        fused = resize(self.bottleneck(torch.cat(pyramid, dim=1)), low.shape[2:])
+        fused = resize(bottleneck(), low.shape[2:])
     return self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
 
 
@@ -155,11 +192,14 @@ def v3plus_hyper_forward(self, x, size=None):
     pyramid = [branch(top) for branch in self.parallel_branches]
     pooled = self.global_branch(top)
     resize = device_resize(self)
-    if resize is None:
-        pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+    if folded_pooling(self, pooled):
+        dec = v3plus_decoder(self, pyramid, low, resize, pooled=pooled)
     else:
-        pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
-    dec = v3plus_decoder(self, pyramid, low, resize)
+        if resize is None:
+            pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+        else:
+            pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
+        dec = v3plus_decoder(self, pyramid, low, resize)
     dec = self.conv_reduce(dec)
     if getattr(self, "wn_mlp", None) is not None:                      # classifier.py:531-550
         b, ch, h, w = dec.shape

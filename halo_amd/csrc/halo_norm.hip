@@ -193,6 +193,215 @@ static void an_launch_bwd(bool want_x, bool want_r, bool raff, unsigned grid, hi
     else hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, true>), gd, b, 0, st, g, y, scale, r_scale, gx, gr, G);
 }
 
+
+// ---------------------------------------------------------------- the image-pooling branch of the v3+ bottleneck as a border-aware bias
+// The last Cg input channels of the bottleneck's 3x3 zero-padded conv are constant planes v[b,c] (the pooled branch, broadcast), so
+// their share of the conv output takes 9 values per (image, output channel): 3 row classes (top row, interior, bottom row) x 3
+// column classes, by which taps fall inside the map.
+//
+//   S[b,o,k]       = sum_c Wg[o,c,k] v[b,c]                                float64 products and sums, a fixed reduction shape
+//   T[b,o,rc,cc]   = fl32(sum_{ky in R(rc)} sum_{kx in C(cc)} S[b,o,ky,kx])  float64, ky then kx ascending, rounded once
+//                    R(top) = {1,2}, R(interior) = {0,1,2}, R(bottom) = {0,1}; C likewise
+//   y              = relu(fl(fl(fl(z + T[b,o,rc(i),cc(j)]) scale[o]) + shift[o]))
+//   gp = y <= 0 ? 0 : g;   g_z = fl(gp scale[o]);   g_T[b,o,rc,cc] = sum over the class's pixels of g_z   (float64)
+//
+// The epilogue is k_affine_relu's plane / chunk walk; scale, shift and the plane's table of 9 entries are block-uniform.  The 16-byte
+// route needs W % 4 == 0, so that a group of four lies in one row.  The class sums: every lane adds its elements into 9 float64
+// accumulators in element order, a workgroup adds its lanes in a fixed LDS tree and writes its own row of the slab, and
+// k_pool_fold_finish adds a plane's rows in ascending order: no atomics, the same bits on every call and every stream.
+
+constexpr int PF_TPB = 256;                    // lanes of the fold pass: channel c goes to lane c % PF_TPB
+
+struct PfGeom {
+    AnGeom a;
+    int H, W;
+};
+
+// the LDS tree of both reductions: 9 float64 per lane, halving strides
+__device__ __forceinline__ void pf_tree(double (*red)[PF_TPB], const double *acc, int t)
+{
+#pragma unroll
+    for (int k = 0; k < 9; ++k) red[k][t] = acc[k];
+    __syncthreads();
+    for (int s = PF_TPB / 2; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) red[k][t] += red[k][t + s];
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(PF_TPB) k_pool_fold_table(const float *__restrict__ w, const float *__restrict__ v, float *__restrict__ T,
+                                                            int Co, int Cg, int64_t c_off, int64_t row_stride)
+{
+    __shared__ double red[9][PF_TPB];
+    const int b = (int)(blockIdx.x / (unsigned)Co), o = (int)(blockIdx.x - (unsigned)b * (unsigned)Co), t = (int)threadIdx.x;
+    const float *wr = w + (size_t)o * (size_t)row_stride + (size_t)c_off * 9;
+    const float *vb = v + (size_t)b * Cg;
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int c = t; c < Cg; c += PF_TPB) {
+        const double vc = (double)vb[c];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[k] += (double)wr[(size_t)c * 9 + k] * vc;
+    }
+    pf_tree(red, acc, t);
+    if (t < 9) {
+        const int rc = t / 3, cc = t - rc * 3;
+        const int y0 = rc == 0 ? 1 : 0, y1 = rc == 2 ? 1 : 2, x0 = cc == 0 ? 1 : 0, x1 = cc == 2 ? 1 : 2;
+        double s = 0.0;
+        for (int ky = y0; ky <= y1; ++ky)
+            for (int kx = x0; kx <= x1; ++kx) s += red[ky * 3 + kx][0];
+        T[(size_t)blockIdx.x * 9 + t] = (float)s;
+    }
+}
+
+// row class of a row: 0 top, 1 interior, 2 bottom
+__device__ __forceinline__ int pf_rc(int row, int H) { return row == 0 ? 0 : row == H - 1 ? 2 : 1; }
+
+template <int GW, bool FULL>
+__device__ __forceinline__ void pf_fwd_chunk(const float *__restrict__ z, float *__restrict__ y, int g0, int n, int H, int W, float sc, float sh,
+                                             const float *__restrict__ t)
+{
+    float zv[AN_U][GW];
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int g = g0 + u * AN_TPB;
+        if (FULL || g < n) an_load<GW>(z + (size_t)g * GW, zv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int g = g0 + u * AN_TPB;
+        if (FULL || g < n) {
+            const unsigned e0 = (unsigned)g * GW, row = e0 / (unsigned)W, col = e0 - row * (unsigned)W;
+            const float *tr = t + pf_rc((int)row, H) * 3;      // the plane's 36-byte table stays in the cache; a copy in registers
+            const float t0 = tr[0], t1 = tr[1], t2 = tr[2];    // picked by selects comes back from the compiler as an LDS array
+            float out[GW];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                const int c = (int)col + e;
+                float s = zv[u][e] + (c == 0 ? t0 : c == W - 1 ? t2 : t1);
+                s = s * sc;
+                s = s + sh;
+                out[e] = s <= 0.0f ? 0.0f : s;
+            }
+            an_store<GW>(y + (size_t)g * GW, out);
+        }
+    }
+}
+
+template <int GW>
+__global__ void __launch_bounds__(AN_TPB) k_pool_fold_fwd(const float *__restrict__ z, const float *__restrict__ T, const float *__restrict__ scale,
+                                                          const float *__restrict__ shift, float *__restrict__ y, PfGeom G)
+{
+    const unsigned plane = blockIdx.x / (unsigned)G.a.cpp;
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.a.cpp), c = (int)(plane % (unsigned)G.a.C);
+    const size_t po = (size_t)plane * G.a.n * GW;
+    const float sc = scale[c], sh = shift[c];
+    const float *t = T + (size_t)plane * 9;
+    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
+    if (G.a.n - base >= AN_CHUNK) pf_fwd_chunk<GW, true>(z + po, y + po, g0, G.a.n, G.H, G.W, sc, sh, t);
+    else pf_fwd_chunk<GW, false>(z + po, y + po, g0, G.a.n, G.H, G.W, sc, sh, t);
+}
+
+template <int GW, bool GZ, bool SUMS, bool FULL>
+__device__ __forceinline__ void pf_bwd_chunk(const float *__restrict__ g, const float *__restrict__ y, float *__restrict__ gz, int g0, int n, int H,
+                                             int W, float sc, double *acc)
+{
+    float gv[AN_U][GW], yv[AN_U][GW];
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int q = g0 + u * AN_TPB;
+        if (FULL || q < n) {
+            an_load<GW>(g + (size_t)q * GW, gv[u]);
+            an_load<GW>(y + (size_t)q * GW, yv[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int q = g0 + u * AN_TPB;
+        if (FULL || q < n) {
+            const unsigned e0 = (unsigned)q * GW, row = e0 / (unsigned)W, col = e0 - row * (unsigned)W;
+            const int rc = pf_rc((int)row, H);
+            float ox[GW];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                const float gp = yv[u][e] <= 0.0f ? 0.0f : gv[u][e];
+                ox[e] = gp * sc;
+                if constexpr (SUMS) {
+                    const int c = (int)col + e, cls = rc * 3 + (c == 0 ? 0 : c == W - 1 ? 2 : 1);
+                    const double d = (double)ox[e];
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) acc[k] += cls == k ? d : 0.0;
+                }
+            }
+            if constexpr (GZ) an_store<GW>(gz + (size_t)q * GW, ox);
+        }
+    }
+}
+
+template <int GW, bool GZ, bool SUMS>
+__global__ void __launch_bounds__(AN_TPB) k_pool_fold_bwd(const float *__restrict__ g, const float *__restrict__ y, const float *__restrict__ scale,
+                                                          float *__restrict__ gz, double *__restrict__ slab, PfGeom G)
+{
+    static_assert(AN_TPB == PF_TPB, "pf_tree is sized for the plane walk's workgroup");
+    __shared__ double red[SUMS ? 9 : 1][PF_TPB];
+    const unsigned plane = blockIdx.x / (unsigned)G.a.cpp;
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.a.cpp), c = (int)(plane % (unsigned)G.a.C);
+    const size_t po = (size_t)plane * G.a.n * GW;
+    const float sc = scale[c];
+    float *zp = GZ ? gz + po : nullptr;
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
+    if (G.a.n - base >= AN_CHUNK) pf_bwd_chunk<GW, GZ, SUMS, true>(g + po, y + po, zp, g0, G.a.n, G.H, G.W, sc, acc);
+    else pf_bwd_chunk<GW, GZ, SUMS, false>(g + po, y + po, zp, g0, G.a.n, G.H, G.W, sc, acc);
+    if constexpr (SUMS) {
+        pf_tree(red, acc, (int)threadIdx.x);
+        if (threadIdx.x < 9) slab[(size_t)blockIdx.x * 9 + threadIdx.x] = red[threadIdx.x][0];
+    }
+}
+
+// g_T[plane][k] = the plane's slab rows added in ascending chunk order
+__global__ void __launch_bounds__(PF_TPB) k_pool_fold_finish(const double *__restrict__ slab, double *__restrict__ gT, int64_t entries, int cpp)
+{
+    const int64_t i = (int64_t)blockIdx.x * PF_TPB + threadIdx.x;
+    if (i >= entries) return;
+    const int64_t plane = i / 9;
+    const int k = (int)(i - plane * 9);
+    double s = 0.0;
+    for (int ch = 0; ch < cpp; ++ch) s += slab[((size_t)plane * cpp + ch) * 9 + k];
+    gT[i] = s;
+}
+
+static int pf_plan(const char *who, int64_t B, int64_t Co, int64_t H, int64_t W, bool vec, PfGeom &G, unsigned &grid)
+{
+    if (B < 1 || Co < 1 || H < 1 || W < 1) return fail(HALO_E_ARG, "%s: empty shape", who);
+    if (H < 2 || W < 2) return fail(HALO_E_ARG, "%s: a %lld x %lld map has no separate border classes (H, W >= 2)", who, (long long)H, (long long)W);
+    if (H > 0x7fffffffLL || W > 0x7fffffffLL || H * W > 0x7fffffffLL - AN_CHUNK)
+        return fail(HALO_E_UNSUPPORTED, "%s: %lld x %lld planes of %lld x %lld", who, (long long)B, (long long)Co, (long long)H, (long long)W);
+    if (int rc = an_plan(who, B, Co, H * W, vec, G.a, grid)) return rc;
+    G.H = (int)H, G.W = (int)W;
+    return HALO_OK;
+}
+
+static bool pf_vec(int64_t W, const void *p0, const void *p1, const void *p2)
+{
+    return W % 4 == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) % 16) == 0;
+}
+
+// rows of the slab per plane: sized for the one-element route, which cuts a plane into the most chunks
+static int64_t pf_slab_rows(int64_t H, int64_t W) { return cdiv(H * W, AN_CHUNK); }
+
+template <int GW>
+static void pf_launch_bwd(bool want_z, bool sums, unsigned grid, hipStream_t st, const float *g, const float *y, const float *scale, float *gz,
+                          double *slab, const PfGeom &G)
+{
+    const dim3 gd(grid), b(AN_TPB);
+    if (want_z && sums) hipLaunchKernelGGL((k_pool_fold_bwd<GW, true, true>), gd, b, 0, st, g, y, scale, gz, slab, G);
+    else if (want_z) hipLaunchKernelGGL((k_pool_fold_bwd<GW, true, false>), gd, b, 0, st, g, y, scale, gz, slab, G);
+    else hipLaunchKernelGGL((k_pool_fold_bwd<GW, false, true>), gd, b, 0, st, g, y, scale, gz, slab, G);
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -228,5 +437,71 @@ extern "C" int halo_affine_relu_bwd(const float *g, const float *y, const float 
     const bool raff = g_r && r_scale;
     if (vec) an_launch_bwd<4>(g_x != nullptr, g_r != nullptr, raff, grid, (hipStream_t)stream, g, y, scale, r_scale, g_x, g_r, G);
     else an_launch_bwd<1>(g_x != nullptr, g_r != nullptr, raff, grid, (hipStream_t)stream, g, y, scale, r_scale, g_x, g_r, G);
+    return check_launch(who);
+}
+
+extern "C" size_t halo_pool_fold_workspace_bytes(int64_t B, int64_t Co, int64_t H, int64_t W)
+{
+    // the shapes pf_plan accepts, each factor bounded before it enters a product: 0 for anything a launch would refuse
+    if (B < 1 || Co < 1 || H < 2 || W < 2 || H > 0x7fffffffLL || W > 0x7fffffffLL || B > 0x7fffffffLL || Co > 0x7fffffffLL) return 0;
+    if (H * W > 0x7fffffffLL - AN_CHUNK || B * Co > 0x7fffffffLL) return 0;
+    const int64_t rows = pf_slab_rows(H, W);                                  // at most 2^21
+    if (B * Co > 0x7fffffffLL / rows) return 0;                                // more rows than a grid has workgroups
+    return align_up((size_t)(B * Co * rows) * 9 * sizeof(double), 256);
+}
+
+extern "C" int halo_pool_fold_table(const float *w, const float *v, float *T, int64_t B, int64_t Co, int64_t Cg, int64_t c_off,
+                                    int64_t row_stride, void *stream)
+{
+    const char *who = "halo_pool_fold_table";
+    if (!w || !v || !T) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (B < 1 || Co < 1 || Cg < 1) return fail(HALO_E_ARG, "%s: empty shape", who);
+    if (c_off < 0 || row_stride < (c_off + Cg) * 9) return fail(HALO_E_ARG, "%s: channels %lld..%lld do not fit a row of %lld elements", who,
+                                                                (long long)c_off, (long long)(c_off + Cg), (long long)row_stride);
+    if (Cg > 0x7fffffffLL / 9 || Co > 0x7fffffffLL || B * Co > 0x7fffffffLL)
+        return fail(HALO_E_UNSUPPORTED, "%s: %lld x %lld tables over %lld channels", who, (long long)B, (long long)Co, (long long)Cg);
+    hipLaunchKernelGGL(k_pool_fold_table, dim3((unsigned)(B * Co)), dim3(PF_TPB), 0, (hipStream_t)stream, w, v, T, (int)Co, (int)Cg, c_off,
+                       row_stride);
+    return check_launch(who);
+}
+
+extern "C" int halo_pool_fold_affine_relu_fwd(const float *z, const float *T, const float *scale, const float *shift, float *y, int64_t B,
+                                              int64_t Co, int64_t H, int64_t W, void *stream)
+{
+    const char *who = "halo_pool_fold_affine_relu_fwd";
+    if (!z || !T || !scale || !shift || !y) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = pf_vec(W, z, y, nullptr);
+    PfGeom G;
+    unsigned grid;
+    if (int rc = pf_plan(who, B, Co, H, W, vec, G, grid)) return rc;
+    if (vec) hipLaunchKernelGGL((k_pool_fold_fwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, z, T, scale, shift, y, G);
+    else hipLaunchKernelGGL((k_pool_fold_fwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, z, T, scale, shift, y, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_pool_fold_affine_relu_bwd(const float *g, const float *y, const float *scale, float *g_z, double *g_T, int64_t B, int64_t Co,
+                                              int64_t H, int64_t W, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "halo_pool_fold_affine_relu_bwd";
+    if (!g || !y || !scale) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = pf_vec(W, g, y, g_z);
+    PfGeom G;
+    unsigned grid;
+    if (int rc = pf_plan(who, B, Co, H, W, vec, G, grid)) return rc;
+    if (!g_z && !g_T) return HALO_OK;                             // nothing is asked for: nothing is launched
+    double *slab = nullptr;
+    if (g_T) {
+        Arena ar(workspace, workspace ? workspace_bytes : 0);
+        slab = ar.take<double>((size_t)grid * 9);
+        if (!slab) return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, halo_pool_fold_workspace_bytes gives %zu", who, workspace_bytes,
+                               halo_pool_fold_workspace_bytes(B, Co, H, W));
+    }
+    if (vec) pf_launch_bwd<4>(g_z != nullptr, g_T != nullptr, grid, (hipStream_t)stream, g, y, scale, g_z, slab, G);
+    else pf_launch_bwd<1>(g_z != nullptr, g_T != nullptr, grid, (hipStream_t)stream, g, y, scale, g_z, slab, G);
+    if (g_T) {
+        const int64_t entries = B * Co * 9;
+        hipLaunchKernelGGL(k_pool_fold_finish, dim3((unsigned)cdiv(entries, PF_TPB)), dim3(PF_TPB), 0, (hipStream_t)stream, slab, g_T, entries,
+                           G.a.cpp);
+    }
     return check_launch(who);
 }

@@ -286,17 +286,20 @@ def use_fused_training_losses(learner_cls):
 # kept as `_unfused_forward`.  Neither install() nor the existing forward changes.
 
 def fused_v3plus_hyper_forward(self, x, size=None):
-    from .core.models.classifier import _tail_modules, broadcast_or_resize, device_resize, hyper_head_tail, v3plus_decoder
+    from .core.models.classifier import _tail_modules, broadcast_or_resize, device_resize, folded_pooling, hyper_head_tail, v3plus_decoder
     from .hfr import weighted_normalize
     low, top = x["low"], x["out"]
     pyramid = [branch(top) for branch in self.parallel_branches]
     pooled = self.global_branch(top)
     resize = device_resize(self)
-    if resize is None:
-        pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+    if folded_pooling(self, pooled):
+        dec = v3plus_decoder(self, pyramid, low, resize, pooled=pooled)
     else:
-        pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
-    dec = v3plus_decoder(self, pyramid, low, resize)
+        if resize is None:
+            pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+        else:
+            pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
+        dec = v3plus_decoder(self, pyramid, low, resize)
     dec = self.conv_reduce(dec)
     if getattr(self, "wn_mlp", None) is not None:
         dec = weighted_normalize(dec, self.wn_mlp)
@@ -408,6 +411,28 @@ def use_fused_decoder_front(head_cls):
         raise TypeError("use_fused_decoder_front: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
                         "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
     head_cls._halo_fused_decoder_front = True
+    return head_cls
+
+
+# ---------------------------------------------------------------- the image-pooling branch folded into the bottleneck's epilogue
+# The last Cg of the bottleneck conv's input channels are global_branch's output, one value per (image, channel) broadcast over the
+# map: a fifth of the largest convolution of the v3+ heads runs over constant planes.  `use_folded_image_pooling(head_cls)` marks a
+# head class that carries one of the package's v3+ forwards; its instances hand the 1 x 1 map to the bottleneck stage without
+# broadcasting it and run halo_amd.aspp.pooled_bottleneck there (core.models.classifier.v3plus_bottleneck: the condition and the
+# fallback).  A class attribute like use_fused_decoder_front's: opt-in, not bound by install(), composes with the other hooks in
+# any order; parameters, module names and state_dict() are untouched.
+
+def use_folded_image_pooling(head_cls):
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward or fused_v3plus_hyper_forward) so that the bottleneck's conv
+    runs over the parallel branches alone and the pooled branch enters its norm + ReLU pass as a border-aware bias.  Returns the
+    class.  Idempotent.  The marked head's results are not the stock chain's bits: the pooled channels' share is summed in float64
+    and rounded once."""
+    if not isinstance(head_cls, type):
+        raise TypeError("use_folded_image_pooling: expected a class, got %r" % (head_cls,))
+    if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
+        raise TypeError("use_folded_image_pooling: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
+                        "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
+    head_cls._halo_folded_image_pooling = True
     return head_cls
 
 

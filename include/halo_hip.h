@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HALO_ABI_VERSION 12
+#define HALO_ABI_VERSION 13
 
 enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4 };
 
@@ -462,6 +462,33 @@ int halo_affine_relu_fwd(const float *x, const float *scale, const float *shift,
                          float *y, int64_t B, int64_t C, int64_t HW, void *stream);
 int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *r_scale, float *g_x, float *g_r, int64_t B,
                          int64_t C, int64_t HW, void *stream);
+
+/* ---- the image-pooling branch of the v3+ bottleneck folded into a border-aware bias (halo_amd/aspp.py) ----
+ *  The bottleneck's 3x3 zero-padded conv reads Cx pyramid channels and Cg channels that are constant planes v[b,c] (the pooled branch,
+ *  broadcast).  The constant planes' share of its output takes 9 values per (image, output channel): 3 row classes (0 top row, 1
+ *  interior, 2 bottom row) x 3 column classes, by which taps fall inside the map.
+ *  w: the conv's (Co, Cx + Cg, 3, 3) f32 weight, read in place: Wg[o,c,k] = w[o row_stride + (c_off + c) 9 + k] with c_off = Cx and
+ *  row_stride = (Cx + Cg) 9 elements; v (B, Cg) f32; T (B, Co, 3, 3) f32; z, y, g, g_z (B, Co, H, W) f32 dense NCHW; scale, shift (Co)
+ *  f32; g_T (B, Co, 3, 3) f64.
+ *    S[b,o,ky,kx] = sum_c Wg[o,c,ky,kx] v[b,c]                       float64 products and sums, channel c on lane c % 256, a fixed tree
+ *    T[b,o,rc,cc] = fl32(sum_{ky in R(rc)} sum_{kx in C(cc)} S)      float64, ky then kx ascending; R(0) = {1,2}, R(1) = {0,1,2},
+ *                                                                    R(2) = {0,1}, C likewise
+ *    y   = relu(fl(fl(fl(z + T[b,o,rc(i),cc(j)]) scale[o]) + shift[o]))       three roundings, never an fma; a NaN stays a NaN
+ *    gp  = y <= 0 ? 0 : g;   g_z = fl(gp scale[o]);   g_T[b,o,rc,cc] = sum over the class's pixels of g_z in float64
+ *  g_T is summed without atomics: a workgroup adds its elements in a fixed order into its own row of the workspace, a second kernel adds
+ *  a plane's rows in ascending order -- the same bits on every call and every stream.  bwd: g_z or g_T may be NULL (g_T NULL needs no
+ *  workspace); with both NULL nothing is launched.  16-byte accesses when W % 4 == 0 and z, y, g, g_z are 16-byte aligned, one element
+ *  per lane otherwise: the same bits.  HALO_E_ARG: a missing pointer, an empty shape, H < 2 or W < 2, a channel range outside the weight
+ *  row; HALO_E_UNSUPPORTED: H W above 2^31 - 1025 or more than 2^31 - 1 workgroups; HALO_E_WORKSPACE: a short workspace.
+ *  halo_pool_fold_workspace_bytes sizes the slab for the route with the most workgroups (B Co ceil(H W / 1024) rows of 72 bytes) and
+ *  returns 0 for a shape the calls refuse, B Co ceil(H W / 1024) above 2^31 - 1 included. */
+size_t halo_pool_fold_workspace_bytes(int64_t B, int64_t Co, int64_t H, int64_t W);
+int halo_pool_fold_table(const float *w, const float *v, float *T, int64_t B, int64_t Co, int64_t Cg, int64_t c_off, int64_t row_stride,
+                         void *stream);
+int halo_pool_fold_affine_relu_fwd(const float *z, const float *T, const float *scale, const float *shift, float *y, int64_t B, int64_t Co,
+                                   int64_t H, int64_t W, void *stream);
+int halo_pool_fold_affine_relu_bwd(const float *g, const float *y, const float *scale, float *g_z, double *g_T, int64_t B, int64_t Co,
+                                   int64_t H, int64_t W, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
