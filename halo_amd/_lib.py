@@ -95,6 +95,8 @@ SIGNATURES = {
     "halo_upcat_dwconv3x3_affine_relu_bwd_weight": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
     "halo_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "halo_masked_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "halo_masked_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_pool_fold_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "halo_pool_fold_table": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "halo_pool_fold_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

@@ -140,8 +140,15 @@ def v3plus_decoder(self, pyramid, low, resize, pooled=None):
     below.  A marked head returns what the same head returns under use_device_resize + use_fused_depthwise on that block, bit for
     bit; that is not bit-equal to the stock F.interpolate / nn.Conv2d chain.
 
+    All three tails hand the decoder's input to halo_amd.hooks.run_decoder: an unmarked head calls self.decoder (behind the fused
+    front: decoder[0]'s pointwise half, then the remaining modules) as before; a block class marked by use_fused_pointwise_norm runs
+    its pointwise norm + ReLU as one pass, and a head class marked by use_fused_decoder_dropout runs such a block and the
+    nn.Dropout2d behind it through halo_amd.norm.norm_relu_dropout2d.  Both return the stock statements' bits.
+
     pooled: None, or -- from a head marked by halo_amd.hooks.use_folded_image_pooling -- global_branch's 1 x 1 output, which pyramid
     then does not hold: the bottleneck runs as v3plus_bottleneck."""
+    from ...hooks import run_decoder
+
     def bottleneck():                            # the one place that says how the bottleneck's output is made
         if pooled is None:
             return self.bottleneck(torch.cat(pyramid, dim=1))
@@ -156,21 +163,18 @@ def v3plus_decoder(self, pyramid, low, resize, pooled=None):
             short = self.shortcut(low)
             if upcat_fallback_reason(top, short, block.depthwise_conv, block.depthwise_bn) is None:
                 dec = upsample_cat_depthwise_bn_relu(top, short, block.depthwise_conv, block.depthwise_bn)
-                dec = block.pointwise_activate(block.pointwise_bn(block.pointwise_conv(dec)))
-                for module in list(self.decoder)[1:]:
-                    dec = module(dec)
-                return dec
+                return run_decoder(self, dec, first_half_done=True)
             if resize is None:
                 fused = F.interpolate(top, size=low.shape[2:], mode="bilinear", align_corners=True)
             else:
                 fused = resize(top, low.shape[2:])
-            return self.decoder(torch.cat([fused, short], dim=1))
+            return run_decoder(self, torch.cat([fused, short], dim=1))
     if resize is None:
         fused = bottleneck()
         fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
     else:
         fused = resize(bottleneck(), low.shape[2:])
-    return self.decoder(torch.cat([fused, self.shortcut(low)], dim=1))
+    return run_decoder(self, torch.cat([fused, self.shortcut(low)], dim=1))
 
 
 def v2_hyper_forward(self, x, size=None):

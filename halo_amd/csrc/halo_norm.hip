@@ -194,6 +194,113 @@ static void an_launch_bwd(bool want_x, bool want_r, bool raff, unsigned grid, hi
 }
 
 
+// ---------------------------------------------------------------- norm + ReLU + Dropout2d: the tail of a separable block behind a dropout
+// nn.Dropout2d multiplies every plane (b, c) by one number m = mask[b * C + c], 0 or fl32(1 / (1 - p)), drawn by the caller.  The
+// same plane / chunk walk with that one more block-uniform operand:
+//
+//   y   = fl(relu(fl(fl(x * scale[c]) + shift[c])) * m)         a NaN stays a NaN; inf * 0 is the stock chain's NaN
+//   g_x = y <= 0 ? 0 : fl(fl(g * m) * scale[c])                 a NaN y lets g through
+//
+// m >= 0, so in a kept plane y > 0 exactly where the ReLU's output is, and the saved y stands in for it.  In a dropped plane y is 0
+// or NaN and either branch gives a zero for a finite g: such a plane's workgroups write zeros and read neither g nor y.  That is
+// the one deviation from autograd, which computes fl(fl(g * 0) * scale) there: a NaN for a non-finite g.
+
+template <int GW, bool FULL>
+__device__ __forceinline__ void an_mask_fwd_chunk(const float *__restrict__ x, float *__restrict__ y, int g0, int n, float sc, float sh, float m)
+{
+    float xv[AN_U][GW];
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int g = g0 + u * AN_TPB;
+        if (FULL || g < n) an_load<GW>(x + (size_t)g * GW, xv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int g = g0 + u * AN_TPB;
+        if (FULL || g < n) {
+            float out[GW];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                float s = xv[u][e] * sc;
+                s = s + sh;
+                s = s <= 0.0f ? 0.0f : s;
+                out[e] = s * m;
+            }
+            an_store<GW>(y + (size_t)g * GW, out);
+        }
+    }
+}
+
+template <int GW>
+__global__ void __launch_bounds__(AN_TPB) k_affine_relu_mask_fwd(const float *__restrict__ x, const float *__restrict__ scale,
+                                                                 const float *__restrict__ shift, const float *__restrict__ mask,
+                                                                 float *__restrict__ y, AnGeom G)
+{
+    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
+    const size_t po = (size_t)plane * G.n * GW;
+    const float sc = scale[c], sh = shift[c], m = mask[plane];
+    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
+    if (G.n - base >= AN_CHUNK) an_mask_fwd_chunk<GW, true>(x + po, y + po, g0, G.n, sc, sh, m);
+    else an_mask_fwd_chunk<GW, false>(x + po, y + po, g0, G.n, sc, sh, m);
+}
+
+template <int GW, bool KEPT, bool FULL>
+__device__ __forceinline__ void an_mask_bwd_chunk(const float *__restrict__ g, const float *__restrict__ y, float *__restrict__ gx, int g0, int n,
+                                                  float sc, float m)
+{
+    float gv[AN_U][GW], yv[AN_U][GW];
+    if constexpr (KEPT) {
+#pragma unroll
+        for (int u = 0; u < AN_U; ++u) {
+            const int q = g0 + u * AN_TPB;
+            if (FULL || q < n) {
+                an_load<GW>(g + (size_t)q * GW, gv[u]);
+                an_load<GW>(y + (size_t)q * GW, yv[u]);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int q = g0 + u * AN_TPB;
+        if (FULL || q < n) {
+            float ox[GW];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                if constexpr (KEPT) {
+                    float t = gv[u][e] * m;
+                    t = t * sc;
+                    ox[e] = yv[u][e] <= 0.0f ? 0.0f : t;
+                } else {
+                    ox[e] = 0.0f;
+                }
+            }
+            an_store<GW>(gx + (size_t)q * GW, ox);
+        }
+    }
+}
+
+template <int GW>
+__global__ void __launch_bounds__(AN_TPB) k_affine_relu_mask_bwd(const float *__restrict__ g, const float *__restrict__ y,
+                                                                 const float *__restrict__ scale, const float *__restrict__ mask,
+                                                                 float *__restrict__ gx, AnGeom G)
+{
+    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
+    const size_t po = (size_t)plane * G.n * GW;
+    const float sc = scale[c], m = mask[plane];
+    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
+    const bool full = G.n - base >= AN_CHUNK;
+    if (m != 0.0f) {                                             // block-uniform: the whole workgroup lies in one plane
+        if (full) an_mask_bwd_chunk<GW, true, true>(g + po, y + po, gx + po, g0, G.n, sc, m);
+        else an_mask_bwd_chunk<GW, true, false>(g + po, y + po, gx + po, g0, G.n, sc, m);
+    } else {
+        if (full) an_mask_bwd_chunk<GW, false, true>(g + po, y + po, gx + po, g0, G.n, sc, m);
+        else an_mask_bwd_chunk<GW, false, false>(g + po, y + po, gx + po, g0, G.n, sc, m);
+    }
+}
+
+
 // ---------------------------------------------------------------- the image-pooling branch of the v3+ bottleneck as a border-aware bias
 // The last Cg input channels of the bottleneck's 3x3 zero-padded conv are constant planes v[b,c] (the pooled branch, broadcast), so
 // their share of the conv output takes 9 values per (image, output channel): 3 row classes (top row, interior, bottom row) x 3
@@ -437,6 +544,34 @@ extern "C" int halo_affine_relu_bwd(const float *g, const float *y, const float 
     const bool raff = g_r && r_scale;
     if (vec) an_launch_bwd<4>(g_x != nullptr, g_r != nullptr, raff, grid, (hipStream_t)stream, g, y, scale, r_scale, g_x, g_r, G);
     else an_launch_bwd<1>(g_x != nullptr, g_r != nullptr, raff, grid, (hipStream_t)stream, g, y, scale, r_scale, g_x, g_r, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_masked_affine_relu_fwd(const float *x, const float *scale, const float *shift, const float *mask, float *y, int64_t B,
+                                           int64_t C, int64_t HW, void *stream)
+{
+    const char *who = "halo_masked_affine_relu_fwd";
+    if (!x || !scale || !shift || !mask || !y) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = an_vec(HW, x, y, nullptr, nullptr);
+    AnGeom G;
+    unsigned grid;
+    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
+    if (vec) hipLaunchKernelGGL((k_affine_relu_mask_fwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, G);
+    else hipLaunchKernelGGL((k_affine_relu_mask_fwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_masked_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *mask, float *g_x, int64_t B,
+                                           int64_t C, int64_t HW, void *stream)
+{
+    const char *who = "halo_masked_affine_relu_bwd";
+    if (!g || !y || !scale || !mask || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = an_vec(HW, g, y, g_x, nullptr);
+    AnGeom G;
+    unsigned grid;
+    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
+    if (vec) hipLaunchKernelGGL((k_affine_relu_mask_bwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
+    else hipLaunchKernelGGL((k_affine_relu_mask_bwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
     return check_launch(who);
 }
 

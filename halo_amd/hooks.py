@@ -358,10 +358,7 @@ def fused_dwsep_forward(self, x):
         x = depthwise_bn_relu(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate)
     else:
         x = torch_statement(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate)
-    x = self.pointwise_conv(x)
-    x = self.pointwise_bn(x)
-    x = self.pointwise_activate(x)
-    return x
+    return pointwise_tail(self, x)
 
 
 def _is_dwsep_class(cls):
@@ -446,8 +443,9 @@ def use_folded_image_pooling(head_cls):
 #   fuse_norm_relu_pairs(module)       instance level: (FrozenBatchNorm2d, nn.ReLU) neighbours that a container calls in sequence --
 #                                      the stem inside the feature extractor's IntermediateLayerGetter, the v3+ heads'
 #                                      parallel_branches[0], global_branch, bottleneck and shortcut.
-# The separable blocks' pointwise_bn + pointwise_activate stay as they are: fusing them needs a forward that composes with
-# use_fused_depthwise, whose results are not bit-equal to the stock depthwise conv, so nothing here switches that on.
+# The separable blocks' pointwise_bn + pointwise_activate, and the nn.Dropout2d behind the hyperbolic head's decoder[1], have hooks
+# of their own further down (use_fused_pointwise_norm, use_fused_decoder_dropout): they act on the second half of a block alone, so
+# they compose with use_fused_depthwise, whose first half is not bit-equal to the stock depthwise conv, without changing its bits.
 
 _RESIDUAL_ATTRS = ("conv1", "bn1", "conv2", "bn2", "relu", "downsample")
 
@@ -560,3 +558,101 @@ def unfuse_norm_relu_pairs(module):
             del m.__dict__["forward"]
             n += isinstance(f, _PairNorm)
     return n
+
+
+# ---------------------------------------------------------------- the pointwise tail of the separable blocks, and the decoder's dropout
+# The second half of every DepthwiseSeparableConv2d is the library's 1 x 1 conv, `pointwise_bn` (a FrozenBatchNorm2d: a broadcast
+# mul and a broadcast add) and `pointwise_activate` (an in-place ReLU); behind decoder[1] the hyperbolic head adds nn.Dropout2d(0.1).
+# Two opt-in marks, neither set by install(), both class attributes that the forwards read when they run:
+#   use_fused_pointwise_norm(block_cls)    a marked block runs halo_amd.norm.norm_relu(pointwise_conv(x), pointwise_bn) -- in
+#                                          fused_dwsep_forward, in v3plus_decoder's fused-front branch, and, on a class that
+#                                          use_fused_depthwise has not bound, in fused_pointwise_forward (stock depthwise half);
+#   use_fused_decoder_dropout(head_cls)    v3plus_decoder walks self.decoder itself and runs a marked separable block that is
+#                                          directly followed by an nn.Dropout2d sibling together with it, as
+#                                          halo_amd.norm.norm_relu_dropout2d (halo_masked_affine_relu_* of halo_norm.hip).
+# Both passes return the stock statements' bits (norm_relu_dropout2d with nn.Dropout2d's use of the generator), so a marked class
+# returns the unmarked class's bits, forward and backward.
+
+def pointwise_tail(block, x):
+    """the second half of a separable block from its depthwise half's output: the three pointwise modules, or -- on a class marked by
+    use_fused_pointwise_norm whose pointwise_activate is an nn.ReLU -- the conv and halo_amd.norm.norm_relu"""
+    x = block.pointwise_conv(x)
+    if getattr(type(block), "_halo_fused_pointwise_norm", False) and type(block.pointwise_activate) is torch.nn.ReLU:
+        from .norm import norm_relu
+        return norm_relu(x, block.pointwise_bn)
+    x = block.pointwise_bn(x)
+    x = block.pointwise_activate(x)
+    return x
+
+
+def fused_pointwise_forward(self, x):
+    x = self.depthwise_conv(x)
+    x = self.depthwise_bn(x)
+    x = self.depthwise_activate(x)
+    return pointwise_tail(self, x)
+
+
+def use_fused_pointwise_norm(block_cls):
+    """Mark a depthwise-separable block class (see use_fused_depthwise) so that pointwise_bn + pointwise_activate run as one pass
+    of halo_amd.norm.norm_relu.  Returns the class.  Idempotent; composes with use_fused_depthwise in either order.  A class whose
+    forward is not fused_dwsep_forward gets fused_pointwise_forward, and the forward that replaces is kept as `_unfused_forward`."""
+    if not _is_dwsep_class(block_cls):
+        raise TypeError("use_fused_pointwise_norm: %r is not a depthwise-separable block class (instances with %s)"
+                        % (block_cls, ", ".join(_DWSEP_ATTRS)))
+    block_cls._halo_fused_pointwise_norm = True
+    if _inherited(block_cls, "forward") not in (fused_dwsep_forward, fused_pointwise_forward):
+        block_cls._unfused_forward = _inherited(block_cls, "forward")
+        block_cls.forward = fused_pointwise_forward
+    return block_cls
+
+
+def use_fused_decoder_dropout(head_cls):
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward or fused_v3plus_hyper_forward) so that a separable block of its
+    decoder marked by use_fused_pointwise_norm and the nn.Dropout2d directly behind it run their norm, ReLU and dropout as one pass
+    (halo_amd.norm.norm_relu_dropout2d: the stock chain's bits and generator use).  Returns the class.  Idempotent."""
+    if not isinstance(head_cls, type):
+        raise TypeError("use_fused_decoder_dropout: expected a class, got %r" % (head_cls,))
+    if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
+        raise TypeError("use_fused_decoder_dropout: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
+                        "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
+    head_cls._halo_fused_decoder_dropout = True
+    return head_cls
+
+
+def depthwise_half(block, x):
+    """the first half of a separable block as the block's own class runs it: halo_amd.dwconv.depthwise_bn_relu under
+    use_fused_depthwise, the three stock statements otherwise"""
+    if _inherited(type(block), "forward") is fused_dwsep_forward and type(block.depthwise_activate) is torch.nn.ReLU:
+        from .dwconv import depthwise_bn_relu
+        return depthwise_bn_relu(x, block.depthwise_conv, block.depthwise_bn, block.depthwise_activate)
+    return block.depthwise_activate(block.depthwise_bn(block.depthwise_conv(x)))
+
+
+def run_decoder(head, dec, first_half_done=False):
+    """head.decoder over dec.  An unmarked head, or a decoder that is no nn.Sequential, calls the container (or, behind the fused
+    front, its modules in order) as before.  A head marked by use_fused_decoder_dropout walks the modules: a separable block marked
+    by use_fused_pointwise_norm, with an nn.ReLU pointwise_activate and an nn.Dropout2d as its next sibling, runs its depthwise
+    half, its 1 x 1 conv and norm_relu_dropout2d with that sibling; every other module is called.  first_half_done: dec is already
+    the output of decoder[0]'s depthwise half (the fused front)."""
+    decoder = head.decoder
+    marked = getattr(type(head), "_halo_fused_decoder_dropout", False) and isinstance(decoder, torch.nn.Sequential)
+    if not marked and not first_half_done:
+        return decoder(dec)
+    modules = list(decoder)
+    i = 0
+    while i < len(modules):
+        m = modules[i]
+        skip_front = first_half_done and i == 0
+        nxt = modules[i + 1] if i + 1 < len(modules) else None
+        pair = (marked and isinstance(nxt, torch.nn.Dropout2d) and getattr(type(m), "_halo_fused_pointwise_norm", False)
+                and all(hasattr(m, a) for a in _DWSEP_ATTRS) and type(m.pointwise_activate) is torch.nn.ReLU
+                and (skip_front or _inherited(type(m), "forward") in (fused_dwsep_forward, fused_pointwise_forward)))
+        if pair:
+            from .norm import norm_relu_dropout2d
+            h = dec if skip_front else depthwise_half(m, dec)
+            dec = norm_relu_dropout2d(m.pointwise_conv(h), m.pointwise_bn, nxt)
+            i += 2
+            continue
+        dec = pointwise_tail(m, dec) if skip_front else m(dec)
+        i += 1
+    return dec

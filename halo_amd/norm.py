@@ -24,6 +24,9 @@ buffers, which the entry holds references to.  load_state_dict and every in-plac
 version is one through a detached alias (`bn.weight.data.mul_()`, or a write through a tensor obtained with .detach() under
 inference mode); call `forget(bn)` after such a write.  A buffer without a version counter (an inference-mode tensor) is never
 cached.
+
+`norm_relu_dropout2d(x, bn, drop)` further down is the same pass with nn.Dropout2d's per-plane multiplier folded in: the tail of a
+separable block and the dropout module behind it (the hyperbolic v3+ head's decoder[1], decoder[2]).
 """
 import weakref
 
@@ -37,13 +40,17 @@ from .hfr import _autocast
 
 _BUFFERS = ("weight", "bias", "running_mean", "running_var")
 _cache = weakref.WeakKeyDictionary()          # norm module -> (the four keyed buffers, their versions, (scale, shift))
-launches = {"fwd": 0, "bwd": 0}               # device launches issued by this module (tests count them)
+# device launches issued by this module (tests count them): "fwd" / "bwd" of norm_relu, "masked_fwd" / "masked_bwd" of
+# norm_relu_dropout2d's own kernels
+launches = {"fwd": 0, "bwd": 0, "masked_fwd": 0, "masked_bwd": 0}
 # A speed rule, not a correctness rule (both sides return the same bits).  When a gradient will be asked for, a forward + backward
 # pair through the Python autograd node costs about 0.16 ms of host time whatever the size; measured alone, back to back, the stock
 # chain's pair is shorter than that below these element counts (2 x 512 x 80 x 160 loses without a residual_bn
 # and wins with one, 2 x 1024 x 80 x 160 wins in every variant).  Smaller tensors that require a gradient run the stock statements;
 # without a gradient (no_grad, inputs that need none) every size is served.  Set both to 0 to serve every size.
-AUTOGRAD_MIN_ELEMENTS = {"plain": 2 * 1024 * 80 * 160, "affine": 2 * 512 * 80 * 160}
+# "masked" is norm_relu_dropout2d's pass with nn.Dropout2d in training mode: the smallest size timed that wins in two separate runs
+# (2 x 512 x 80 x 160 wins by 2 to 7 %, 1 x 512 x 90 x 160 loses, the decoder's 2 x 512 x 160 x 320 wins x2.8).
+AUTOGRAD_MIN_ELEMENTS = {"plain": 2 * 1024 * 80 * 160, "affine": 2 * 512 * 80 * 160, "masked": 2 * 512 * 80 * 160}
 
 
 def torch_statement(x, bn, residual=None, residual_bn=None):
@@ -183,4 +190,82 @@ def fused_norm_relu(x, bn, residual=None, residual_bn=None):
     return _NormReluFn.apply(x, scale, shift, residual, r_scale, r_shift)
 
 
-__all__ = ["norm_relu", "torch_statement", "fallback_reason", "cached_scale_shift", "forget"]
+# ---------------------------------------------------------------- norm + ReLU + Dropout2d
+# The pointwise tail of a separable block with the nn.Dropout2d that follows it (the hyperbolic v3+ head's decoder[1], decoder[2]):
+#
+#     drop(F.relu(bn(x), inplace=True))
+#
+# ATen's feature dropout (_dropout_impl) draws one number per (image, channel) -- noise = x.new_empty((B, C, 1, 1)).bernoulli_(1 - p)
+# .div_(1 - p) -- and multiplies.  norm_relu_dropout2d draws the same tensor with the same statements, so the generator moves as it
+# does under nn.Dropout2d and a seeded run has nn.Dropout2d's bits, and hands it to halo_masked_affine_relu_fwd / _bwd as the
+# per-plane multiplier.
+
+def dropout_statement(x, bn, drop):
+    """the stock statements: the block's pointwise norm and in-place ReLU, then the dropout module"""
+    return drop(F.relu(bn(x), inplace=True))
+
+
+def dropout_fallback_reason(x, bn, drop):
+    """why norm_relu_dropout2d(x, bn, drop) runs the torch statements (None: a fused pass serves it -- the masked one when drop is
+    in training mode with 0 < p < 1, norm_relu's otherwise).  Reads no device memory."""
+    if not isinstance(drop, nn.Dropout2d):
+        return "drop is not an nn.Dropout2d"
+    if drop.inplace:
+        return "the dropout is in place"
+    if not drop.training or drop.p == 0:
+        return fallback_reason(x, bn)                      # nothing is drawn: relu(bn(x)) alone
+    if drop.p >= 1:
+        return "p = 1 drops every plane"
+    reason = _envelope_reason(x, bn, None, None)
+    if reason is None and torch.is_grad_enabled() and getattr(x, "requires_grad", False):
+        least = AUTOGRAD_MIN_ELEMENTS.get("masked", 0)
+        if x.numel() < least:
+            return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (x.numel(), least)
+    return reason
+
+
+class _NormReluDropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, noise):
+        B, C, H, W = x.shape
+        y = torch.empty_like(x)
+        launches["masked_fwd"] += 1
+        _lib.check(_lib.lib().halo_masked_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(noise), _lib.ptr(y),
+                                                          B, C, H * W, _lib.stream_ptr(x.device)), "halo_masked_affine_relu_fwd")
+        ctx.save_for_backward(y, scale, noise)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, scale, noise = ctx.saved_tensors
+        B, C, H, W = y.shape
+        gx = None
+        if ctx.needs_input_grad[0]:
+            g = g.to(device=y.device, dtype=torch.float32).contiguous()
+            gx = torch.empty_like(y)
+            launches["masked_bwd"] += 1
+            _lib.check(_lib.lib().halo_masked_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(noise), _lib.ptr(gx),
+                                                              B, C, H * W, _lib.stream_ptr(y.device)), "halo_masked_affine_relu_bwd")
+        return gx, None, None, None
+
+
+def norm_relu_dropout2d(x, bn, drop):
+    """drop(relu(bn(x))) of a frozen norm and an nn.Dropout2d, x (B, C, H, W): the stock chain's bits, and the stock chain's use of
+    the random generator (one bernoulli_ over (B, C, 1, 1) in training mode with 0 < p < 1, nothing otherwise).  Differentiable
+    w.r.t. x; x is not modified; the backward keeps y, scale and the noise tensor.  One deviation, in the backward alone: the ReLU's
+    mask is read off the saved y, which is 0 in a dropped plane, so a non-finite output gradient in a dropped plane gives 0 where
+    autograd gives NaN; for finite gradients the bits are autograd's.  Outside the served envelope (dropout_fallback_reason) it
+    returns dropout_statement(x, bn, drop)."""
+    if dropout_fallback_reason(x, bn, drop) is not None:
+        return dropout_statement(x, bn, drop)
+    if not drop.training or drop.p == 0:
+        return fused_norm_relu(x, bn)
+    B, C = x.shape[:2]
+    noise = x.new_empty((B, C, 1, 1)).bernoulli_(1 - drop.p).div_(1 - drop.p)          # ATen's _dropout_impl, feature dropout
+    scale, shift = cached_scale_shift(bn)
+    return _NormReluDropFn.apply(x, scale, shift, noise)
+
+
+__all__ = ["norm_relu", "torch_statement", "fallback_reason", "cached_scale_shift", "forget", "norm_relu_dropout2d",
+           "dropout_statement", "dropout_fallback_reason"]

@@ -463,6 +463,21 @@ int halo_affine_relu_fwd(const float *x, const float *scale, const float *shift,
 int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *r_scale, float *g_x, float *g_r, int64_t B,
                          int64_t C, int64_t HW, void *stream);
 
+/* ---- frozen norm + ReLU + Dropout2d: the pointwise tail of a separable block and the dropout behind it (halo_amd/norm.py) ----
+ *  x, y, g, g_x (B, C, HW) f32 dense NCHW planes; scale, shift (C) f32; mask (B, C) f32: the multiplier of plane (b, c), 0 or
+ *  fl32(1 / (1 - p)), drawn by the caller (nn.Dropout2d's noise tensor).
+ *    y   = fl(relu(fl(fl(x scale[c]) + shift[c])) mask[b,c])        every product and sum rounded on its own, a NaN stays a NaN
+ *    g_x = y <= 0 ? 0 : fl(fl(g mask[b,c]) scale[c])                a NaN y lets g through
+ *  The bits of `dropout2d(relu_(x * scale + bias))` and, for a finite g, of its autograd backward.  The forward reads x in dropped
+ *  planes too (inf * 0 is a NaN there, as in the stock chain).  The backward writes zeros for a plane whose mask is 0 without
+ *  reading g or y: a non-finite g in a dropped plane gives 0 where autograd gives a NaN.  y must not overlap x; g_x must not
+ *  overlap g or y.  Routes, alignment rule and limits are those of the pair above.  HALO_E_ARG: an empty shape or a missing
+ *  pointer; HALO_E_UNSUPPORTED: HW above 2^31 - 1025 or more than 2^31 - 1 workgroups. */
+int halo_masked_affine_relu_fwd(const float *x, const float *scale, const float *shift, const float *mask, float *y, int64_t B, int64_t C,
+                                int64_t HW, void *stream);
+int halo_masked_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *mask, float *g_x, int64_t B, int64_t C,
+                                int64_t HW, void *stream);
+
 /* ---- the image-pooling branch of the v3+ bottleneck folded into a border-aware bias (halo_amd/aspp.py) ----
  *  The bottleneck's 3x3 zero-padded conv reads Cx pyramid channels and Cg channels that are constant planes v[b,c] (the pooled branch,
  *  broadcast).  The constant planes' share of its output takes 9 values per (image, output channel): 3 row classes (0 top row, 1
