@@ -97,6 +97,8 @@ SIGNATURES = {
     "halo_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_masked_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_masked_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "halo_dropout_pair_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "halo_dropout_pair_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_pool_fold_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "halo_pool_fold_table": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "halo_pool_fold_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

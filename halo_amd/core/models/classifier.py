@@ -128,9 +128,9 @@ def v3plus_bottleneck(self, pyramid, pooled, resize):
     return self.bottleneck(torch.cat(pyramid_with_pooled(self, pyramid, pooled, pyramid[0].shape[2:], resize), dim=1))
 
 
-def v3plus_decoder(self, pyramid, low, resize, pooled=None):
+def v3plus_decoder(self, pyramid, low, resize, pooled=None, run=None):
     """The v3+ heads from the ASPP pyramid to the decoder's output (classifier.py:520-527): bottleneck, resize to the low-level
-    map, concat with the shortcut, decoder.  Both package forwards call it.
+    map, concat with the shortcut, decoder.  Every v3+ forward of the package calls it.
 
     A head class marked by halo_amd.hooks.use_fused_decoder_front runs the front of the decoder -- the resize, the concat and the
     depthwise half of decoder[0] -- as halo_amd.dwconv.upsample_cat_depthwise_bn_relu, which stores neither the resized nor the
@@ -146,8 +146,12 @@ def v3plus_decoder(self, pyramid, low, resize, pooled=None):
     nn.Dropout2d behind it through halo_amd.norm.norm_relu_dropout2d.  Both return the stock statements' bits.
 
     pooled: None, or -- from a head marked by halo_amd.hooks.use_folded_image_pooling -- global_branch's 1 x 1 output, which pyramid
-    then does not hold: the bottleneck runs as v3plus_bottleneck."""
-    from ...hooks import run_decoder
+    then does not hold: the bottleneck runs as v3plus_bottleneck.
+
+    run: None, or the walk that takes run_decoder's place and arguments (v3plus_forward's old decoder layout hands in
+    halo_amd.hooks.run_decoder_pair, whose two results come back as they are)."""
+    if run is None:
+        from ...hooks import run_decoder as run
 
     def bottleneck():                            # the one place that says how the bottleneck's output is made
         if pooled is None:
@@ -163,18 +167,18 @@ def v3plus_decoder(self, pyramid, low, resize, pooled=None):
             short = self.shortcut(low)
             if upcat_fallback_reason(top, short, block.depthwise_conv, block.depthwise_bn) is None:
                 dec = upsample_cat_depthwise_bn_relu(top, short, block.depthwise_conv, block.depthwise_bn)
-                return run_decoder(self, dec, first_half_done=True)
+                return run(self, dec, first_half_done=True)
             if resize is None:
                 fused = F.interpolate(top, size=low.shape[2:], mode="bilinear", align_corners=True)
             else:
                 fused = resize(top, low.shape[2:])
-            return run_decoder(self, torch.cat([fused, short], dim=1))
+            return run(self, torch.cat([fused, short], dim=1))
     if resize is None:
         fused = bottleneck()
         fused = F.interpolate(fused, size=low.shape[2:], mode="bilinear", align_corners=True)
     else:
         fused = resize(bottleneck(), low.shape[2:])
-    return run_decoder(self, torch.cat([fused, self.shortcut(low)], dim=1))
+    return run(self, torch.cat([fused, self.shortcut(low)], dim=1))
 
 
 def v2_hyper_forward(self, x, size=None):
@@ -212,6 +216,48 @@ def v3plus_hyper_forward(self, x, size=None):
         dec = F.normalize(dec.reshape(b, ch, h * w), dim=-1).reshape(b, ch, h, w) * weights
     mapper, seg = _tail_modules(self)
     return hyper_head_tail(dec, mapper, seg, size=size, resize_embed=False, resize=resize)
+
+
+def v3plus_forward(self, x, size=None):
+    """forward of DepthwiseSeparableASPP (classifier.py:248-316), the Euclidean DeepLab-v3+ head: the instance's own modules on the
+    helpers v3plus_hyper_forward uses, so the class marks of halo_amd.hooks act on it as they do there.  Returns (out, decoder_out);
+    `size` resizes out alone.
+
+    New layout (`old_decoder` false): decoder, conv_reduce and the wn_mlp statement where the instance has them -- halo_amd.hfr's
+    weighted_normalize on a class marked by use_fused_feature_reweighting, its torch_statement otherwise -- then cls_conv.
+    Old layout: decoder = Sequential(block, block, Dropout2d, Conv2d); decoder_out is decoder[1]'s output, the remaining modules
+    run on it (halo_amd.hooks.run_decoder_pair)."""
+    from ...hooks import run_decoder_pair
+    low, top = x["low"], x["out"]
+    pyramid = [branch(top) for branch in self.parallel_branches]
+    pooled = self.global_branch(top)
+    # the mark is about the device backward's atomics: on CPU tensors, which no operator serves, every resize is the stock statement --
+    # the 1 x 1 pooled map's too, whose broadcast has F.interpolate's values but sums its gradient in another order
+    resize = device_resize(self) if top.is_cuda else None
+    run = run_decoder_pair if self.old_decoder else None
+    if folded_pooling(self, pooled):
+        dec = v3plus_decoder(self, pyramid, low, resize, pooled=pooled, run=run)
+    else:
+        if resize is None:
+            pyramid.append(F.interpolate(pooled, size=top.shape[2:], mode="bilinear", align_corners=True))
+        else:
+            pyramid.append(broadcast_or_resize(pooled, top.shape[2:], resize))
+        dec = v3plus_decoder(self, pyramid, low, resize, run=run)
+    if self.old_decoder:
+        dec, out = dec
+    else:
+        if self.conv_reduce is not None:
+            dec = self.conv_reduce(dec)
+        if self.wn_mlp is not None:                                        # classifier.py:283-304
+            from ... import hfr
+            fused = getattr(type(self), "_halo_fused_feature_reweighting", False)
+            dec = hfr.weighted_normalize(dec, self.wn_mlp) if fused else hfr.torch_statement(dec, self.wn_mlp)
+        out = self.cls_conv(dec)
+    if size is not None and resize is not None:
+        out = resize(out, size)
+    elif size is not None:
+        out = F.interpolate(out, size=size, mode="bilinear", align_corners=True)
+    return out, dec
 
 
 class ASPP_Classifier_V2_Hyper(nn.Module):

@@ -301,6 +301,136 @@ __global__ void __launch_bounds__(AN_TPB) k_affine_relu_mask_bwd(const float *__
 }
 
 
+// ---------------------------------------------------------------- norm + ReLU + Dropout2d with BOTH tensors kept
+// The Euclidean v3+ head's old decoder layout returns the tensor in front of its nn.Dropout2d and feeds the one behind it to the
+// classifier conv, so the pass has two outputs and its backward two incoming gradients, either of which may be absent:
+//
+//   y   = relu(fl(fl(x * scale[c]) + shift[c]))                 halo_affine_relu_fwd's statements
+//   z   = fl(y * m)                                             m = mask[b * C + c]; inf * 0 is the stock chain's NaN
+//   g   = g_y,  fl(g_z * m)  or  fl(g_y + fl(g_z * m))          the product first, then autograd's accumulation
+//   g_x = fl((y <= 0 ? 0 : g) * scale[c])                       a NaN y lets g through
+//
+// y is the ReLU's own output here, so the gate is autograd's in every plane.  In a dropped plane (m == 0) g_z is not read: its term
+// is taken as 0, which it is for a finite g_z (autograd has a NaN for a non-finite one: section 18's deviation).  With g_y absent
+// such a plane's workgroups write zeros and read nothing.
+
+template <int GW, bool FULL>
+__device__ __forceinline__ void an_pair_fwd_chunk(const float *__restrict__ x, float *__restrict__ y, float *__restrict__ z, int g0, int n,
+                                                  float sc, float sh, float m)
+{
+    float xv[AN_U][GW];
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int g = g0 + u * AN_TPB;
+        if (FULL || g < n) an_load<GW>(x + (size_t)g * GW, xv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int g = g0 + u * AN_TPB;
+        if (FULL || g < n) {
+            float oy[GW], oz[GW];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                float s = xv[u][e] * sc;
+                s = s + sh;
+                oy[e] = s <= 0.0f ? 0.0f : s;
+                oz[e] = oy[e] * m;
+            }
+            an_store<GW>(y + (size_t)g * GW, oy);
+            an_store<GW>(z + (size_t)g * GW, oz);
+        }
+    }
+}
+
+template <int GW>
+__global__ void __launch_bounds__(AN_TPB) k_affine_relu_pair_fwd(const float *__restrict__ x, const float *__restrict__ scale,
+                                                                 const float *__restrict__ shift, const float *__restrict__ mask,
+                                                                 float *__restrict__ y, float *__restrict__ z, AnGeom G)
+{
+    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
+    const size_t po = (size_t)plane * G.n * GW;
+    const float sc = scale[c], sh = shift[c], m = mask[plane];
+    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
+    if (G.n - base >= AN_CHUNK) an_pair_fwd_chunk<GW, true>(x + po, y + po, z + po, g0, G.n, sc, sh, m);
+    else an_pair_fwd_chunk<GW, false>(x + po, y + po, z + po, g0, G.n, sc, sh, m);
+}
+
+// GY / GZ: which of the two gradients this workgroup reads (neither: it writes zeros)
+template <int GW, bool GY, bool GZ, bool FULL>
+__device__ __forceinline__ void an_pair_bwd_chunk(const float *__restrict__ gy, const float *__restrict__ gz, const float *__restrict__ y,
+                                                  float *__restrict__ gx, int g0, int n, float sc, float m)
+{
+    float av[AN_U][GW], bv[AN_U][GW], yv[AN_U][GW];
+    if constexpr (GY || GZ) {
+#pragma unroll
+        for (int u = 0; u < AN_U; ++u) {
+            const int q = g0 + u * AN_TPB;
+            if (FULL || q < n) {
+                if constexpr (GY) an_load<GW>(gy + (size_t)q * GW, av[u]);
+                if constexpr (GZ) an_load<GW>(gz + (size_t)q * GW, bv[u]);
+                an_load<GW>(y + (size_t)q * GW, yv[u]);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < AN_U; ++u) {
+        const int q = g0 + u * AN_TPB;
+        if (FULL || q < n) {
+            float ox[GW];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) {
+                if constexpr (GY || GZ) {
+                    float t;
+                    if constexpr (GZ) {
+                        t = bv[u][e] * m;
+                        if constexpr (GY) t = av[u][e] + t;
+                    } else {
+                        t = av[u][e];
+                    }
+                    t = yv[u][e] <= 0.0f ? 0.0f : t;
+                    ox[e] = t * sc;
+                } else {
+                    ox[e] = 0.0f;
+                }
+            }
+            an_store<GW>(gx + (size_t)q * GW, ox);
+        }
+    }
+}
+
+template <int GW, bool GY, bool GZ>
+__global__ void __launch_bounds__(AN_TPB) k_affine_relu_pair_bwd(const float *__restrict__ gy, const float *__restrict__ gz,
+                                                                 const float *__restrict__ y, const float *__restrict__ scale,
+                                                                 const float *__restrict__ mask, float *__restrict__ gx, AnGeom G)
+{
+    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
+    const size_t po = (size_t)plane * G.n * GW;
+    const float sc = scale[c], m = GZ ? mask[plane] : 1.0f;
+    const float *ap = GY ? gy + po : nullptr, *bp = GZ ? gz + po : nullptr;
+    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
+    const bool full = G.n - base >= AN_CHUNK;
+    if (!GZ || m != 0.0f) {                                      // block-uniform: the whole workgroup lies in one plane
+        if (full) an_pair_bwd_chunk<GW, GY, GZ, true>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
+        else an_pair_bwd_chunk<GW, GY, GZ, false>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
+    } else {                                                     // a dropped plane: g_z's term is 0
+        if (full) an_pair_bwd_chunk<GW, GY, false, true>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
+        else an_pair_bwd_chunk<GW, GY, false, false>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
+    }
+}
+
+template <int GW>
+static void an_launch_pair_bwd(bool has_y, bool has_z, unsigned grid, hipStream_t st, const float *gy, const float *gz, const float *y,
+                               const float *scale, const float *mask, float *gx, const AnGeom &G)
+{
+    const dim3 gd(grid), b(AN_TPB);
+    if (has_y && has_z) hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW, true, true>), gd, b, 0, st, gy, gz, y, scale, mask, gx, G);
+    else if (has_z) hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW, false, true>), gd, b, 0, st, gy, gz, y, scale, mask, gx, G);
+    else hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW, true, false>), gd, b, 0, st, gy, gz, y, scale, mask, gx, G);
+}
+
+
 // ---------------------------------------------------------------- the image-pooling branch of the v3+ bottleneck as a border-aware bias
 // The last Cg input channels of the bottleneck's 3x3 zero-padded conv are constant planes v[b,c] (the pooled branch, broadcast), so
 // their share of the conv output takes 9 values per (image, output channel): 3 row classes (top row, interior, bottom row) x 3
@@ -572,6 +702,35 @@ extern "C" int halo_masked_affine_relu_bwd(const float *g, const float *y, const
     if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
     if (vec) hipLaunchKernelGGL((k_affine_relu_mask_bwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
     else hipLaunchKernelGGL((k_affine_relu_mask_bwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_dropout_pair_fwd(const float *x, const float *scale, const float *shift, const float *mask, float *y, float *z, int64_t B,
+                                     int64_t C, int64_t HW, void *stream)
+{
+    const char *who = "halo_dropout_pair_fwd";
+    if (!x || !scale || !shift || !mask || !y || !z) return fail(HALO_E_ARG, "%s: null argument", who);
+    const bool vec = an_vec(HW, x, y, z, nullptr);
+    AnGeom G;
+    unsigned grid;
+    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
+    if (vec) hipLaunchKernelGGL((k_affine_relu_pair_fwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, z, G);
+    else hipLaunchKernelGGL((k_affine_relu_pair_fwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, z, G);
+    return check_launch(who);
+}
+
+extern "C" int halo_dropout_pair_bwd(const float *g_y, const float *g_z, const float *y, const float *scale, const float *mask, float *g_x,
+                                     int64_t B, int64_t C, int64_t HW, void *stream)
+{
+    const char *who = "halo_dropout_pair_bwd";
+    if (!y || !scale || !mask || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (!g_y && !g_z) return fail(HALO_E_ARG, "%s: null argument: neither g_y nor g_z is given", who);
+    const bool vec = an_vec(HW, g_y, g_z, y, g_x);
+    AnGeom G;
+    unsigned grid;
+    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
+    if (vec) an_launch_pair_bwd<4>(g_y != nullptr, g_z != nullptr, grid, (hipStream_t)stream, g_y, g_z, y, scale, mask, g_x, G);
+    else an_launch_pair_bwd<1>(g_y != nullptr, g_z != nullptr, grid, (hipStream_t)stream, g_y, g_z, y, scale, mask, g_x, G);
     return check_launch(who);
 }
 

@@ -309,7 +309,13 @@ def fused_v3plus_hyper_forward(self, x, size=None):
 
 def use_fused_feature_reweighting(head_cls):
     """Bind fused_v3plus_hyper_forward on a DeepLab-v3+ hyperbolic head class (the reference's DepthwiseSeparableASPP_Hyper or
-    halo_amd's drop-in).  Returns the class; the forward it replaced is kept as `_unfused_forward`."""
+    halo_amd's drop-in).  Returns the class; the forward it replaced is kept as `_unfused_forward`.  A class that carries
+    v3plus_forward (use_v3plus_forward: the Euclidean head, which has no conv_seg) keeps that forward and gets a class mark that it
+    reads: its wn_mlp statement then runs halo_amd.hfr.weighted_normalize."""
+    from .core.models.classifier import v3plus_forward
+    if isinstance(head_cls, type) and _inherited(head_cls, "forward") is v3plus_forward:
+        head_cls._halo_fused_feature_reweighting = True
+        return head_cls
     if head_cls.__dict__.get("forward") is fused_v3plus_hyper_forward:
         return head_cls
     head_cls._unfused_forward = _inherited(head_cls, "forward")
@@ -320,13 +326,14 @@ def use_fused_feature_reweighting(head_cls):
 # ---------------------------------------------------------------- resizes of the training paths on the device operator
 # Under training every align_corners resize of the package's forwards is an F.interpolate, whose device backward scatters float
 # atomic adds: the one source of run-to-run differences in a step's gradients.  `use_device_resize(cls)` marks a head class (one that
-# carries v2_hyper_forward, v3plus_hyper_forward or fused_v3plus_hyper_forward) or a learner class (fused_training_step's
+# carries v2_hyper_forward, v3plus_hyper_forward, fused_v3plus_hyper_forward or v3plus_forward) or a learner class (fused_training_step's
 # LocalConsistentLoss input): marked classes resize through halo_amd.resize.resize_or_interpolate -- halo_bilinear_upsample forward,
 # its gather adjoint backward -- and broadcast the v3+ head's 1 x 1 global-pooling branch.  Nothing changes for an unmarked class.
 
 def _package_forwards():
-    from .core.models.classifier import v2_hyper_forward, v3plus_hyper_forward
-    return (v2_hyper_forward, v3plus_hyper_forward, fused_v3plus_hyper_forward)
+    """the v2 forward, then the v3+ ones"""
+    from .core.models.classifier import v2_hyper_forward, v3plus_forward, v3plus_hyper_forward
+    return (v2_hyper_forward, v3plus_hyper_forward, fused_v3plus_hyper_forward, v3plus_forward)
 
 
 def use_device_resize(cls):
@@ -336,7 +343,8 @@ def use_device_resize(cls):
         raise TypeError("use_device_resize: expected a class, got %r" % (cls,))
     if _training_protocol(cls) is None and not any(_inherited(cls, "forward") is f for f in _package_forwards()):
         raise TypeError("use_device_resize: %s is neither a learner (%s) nor a head class that carries one of halo_amd's forwards; "
-                        "bind one first with halo_amd.install() or use_fused_feature_reweighting" % (cls.__name__, ", ".join(_PROTOCOLS)))
+                        "bind one first with halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward"
+                        % (cls.__name__, ", ".join(_PROTOCOLS)))
     cls._halo_device_resize = True
     return cls
 
@@ -398,15 +406,15 @@ def use_fused_depthwise(block_cls):
 # other hooks in any order; parameters, module names and state_dict() are untouched.
 
 def use_fused_decoder_front(head_cls):
-    """Mark a v3+ head class (one that carries v3plus_hyper_forward or fused_v3plus_hyper_forward) so that the resize, the concat
-    and the depthwise half of decoder[0] run as one HIP pass.  Returns the class.  Idempotent.  The marked head's results are
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward, fused_v3plus_hyper_forward or v3plus_forward) so that the
+    resize, the concat and the depthwise half of decoder[0] run as one HIP pass.  Returns the class.  Idempotent.  The marked head's results are
     those of the head under use_device_resize + use_fused_depthwise on that block, bit for bit -- not those of the stock
     F.interpolate / nn.Conv2d chain."""
     if not isinstance(head_cls, type):
         raise TypeError("use_fused_decoder_front: expected a class, got %r" % (head_cls,))
     if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
         raise TypeError("use_fused_decoder_front: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
-                        "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
+                        "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
     head_cls._halo_fused_decoder_front = True
     return head_cls
 
@@ -420,15 +428,15 @@ def use_fused_decoder_front(head_cls):
 # any order; parameters, module names and state_dict() are untouched.
 
 def use_folded_image_pooling(head_cls):
-    """Mark a v3+ head class (one that carries v3plus_hyper_forward or fused_v3plus_hyper_forward) so that the bottleneck's conv
-    runs over the parallel branches alone and the pooled branch enters its norm + ReLU pass as a border-aware bias.  Returns the
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward, fused_v3plus_hyper_forward or v3plus_forward) so that the
+    bottleneck's conv runs over the parallel branches alone and the pooled branch enters its norm + ReLU pass as a border-aware bias.  Returns the
     class.  Idempotent.  The marked head's results are not the stock chain's bits: the pooled channels' share is summed in float64
     and rounded once."""
     if not isinstance(head_cls, type):
         raise TypeError("use_folded_image_pooling: expected a class, got %r" % (head_cls,))
     if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
         raise TypeError("use_folded_image_pooling: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
-                        "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
+                        "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
     head_cls._halo_folded_image_pooling = True
     return head_cls
 
@@ -607,14 +615,14 @@ def use_fused_pointwise_norm(block_cls):
 
 
 def use_fused_decoder_dropout(head_cls):
-    """Mark a v3+ head class (one that carries v3plus_hyper_forward or fused_v3plus_hyper_forward) so that a separable block of its
-    decoder marked by use_fused_pointwise_norm and the nn.Dropout2d directly behind it run their norm, ReLU and dropout as one pass
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward, fused_v3plus_hyper_forward or v3plus_forward) so that a
+    separable block of its decoder marked by use_fused_pointwise_norm and the nn.Dropout2d directly behind it run their norm, ReLU and dropout as one pass
     (halo_amd.norm.norm_relu_dropout2d: the stock chain's bits and generator use).  Returns the class.  Idempotent."""
     if not isinstance(head_cls, type):
         raise TypeError("use_fused_decoder_dropout: expected a class, got %r" % (head_cls,))
     if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
         raise TypeError("use_fused_decoder_dropout: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
-                        "halo_amd.install() or use_fused_feature_reweighting" % head_cls.__name__)
+                        "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
     head_cls._halo_fused_decoder_dropout = True
     return head_cls
 
@@ -656,3 +664,69 @@ def run_decoder(head, dec, first_half_done=False):
         dec = pointwise_tail(m, dec) if skip_front else m(dec)
         i += 1
     return dec
+
+
+def run_decoder_pair(head, dec, first_half_done=False):
+    """The old decoder layout of the Euclidean v3+ head, Sequential(block, block, Dropout2d, Conv2d), over dec (classifier.py:
+    308-312): returns (decoder_out, out) -- decoder[1]'s output, and what the remaining modules make of it.  Unmarked, the walk is
+    the reference's loop over the modules.  On a head class marked by use_fused_decoder_dropout, a decoder[1] that run_decoder
+    would pair with its nn.Dropout2d sibling (a block marked by use_fused_pointwise_norm with an nn.ReLU pointwise_activate) runs
+    its depthwise half, its 1 x 1 conv and halo_amd.norm.norm_relu_dropout2d_pair, whose first result is decoder_out and whose
+    second goes on to decoder[3:].  first_half_done: as in run_decoder."""
+    modules = list(head.decoder)
+    marked = getattr(type(head), "_halo_fused_decoder_dropout", False) and isinstance(head.decoder, torch.nn.Sequential)
+    dec = pointwise_tail(modules[0], dec) if first_half_done else modules[0](dec)
+    m, nxt = modules[1], modules[2] if len(modules) > 2 else None
+    pair = (marked and isinstance(nxt, torch.nn.Dropout2d) and getattr(type(m), "_halo_fused_pointwise_norm", False)
+            and all(hasattr(m, a) for a in _DWSEP_ATTRS) and type(m.pointwise_activate) is torch.nn.ReLU
+            and _inherited(type(m), "forward") in (fused_dwsep_forward, fused_pointwise_forward))
+    if pair:
+        from .norm import norm_relu_dropout2d_pair
+        decoder_out, dec = norm_relu_dropout2d_pair(m.pointwise_conv(depthwise_half(m, dec)), m.pointwise_bn, nxt)
+        rest = modules[3:]
+    else:
+        decoder_out = dec = m(dec)
+        rest = modules[2:]
+    for m in rest:
+        dec = m(dec)
+    return decoder_out, dec
+
+
+# ---------------------------------------------------------------- the Euclidean DeepLab-v3+ head on the package's forward
+# DepthwiseSeparableASPP (core/models/classifier.py:88-316) is the head of configs/gtav/ripu.yaml (HYPER False): the hyperbolic
+# v3+ head's ASPP pyramid, bottleneck, shortcut and decoder in front of a classifier conv.  `use_v3plus_forward(head_cls)` binds
+# halo_amd.core.models.classifier.v3plus_forward, which is written on the helpers of v3plus_hyper_forward: unmarked it runs the
+# reference's statements, and use_device_resize, use_fused_decoder_front, use_folded_image_pooling, use_fused_decoder_dropout and
+# use_fused_feature_reweighting accept the bound class.  Opt-in, not bound by install(); parameters, module names and state_dict()
+# are untouched.
+
+_V3PLUS_ATTRS = ("parallel_branches", "global_branch", "bottleneck", "shortcut", "decoder", "old_decoder")
+
+
+def _is_v3plus_class(cls):
+    """the reference's DepthwiseSeparableASPP (by name), or an nn.Module class whose instances carry the six attributes and no
+    conv_seg (class attributes, or names its __init__ methods assign: nothing is constructed)"""
+    if not isinstance(cls, type) or not issubclass(cls, torch.nn.Module):
+        return False
+    if any(k.__name__ == "DepthwiseSeparableASPP" for k in cls.__mro__):
+        return True
+    names = set()
+    for klass in cls.__mro__:
+        init = klass.__dict__.get("__init__")
+        names.update(getattr(getattr(init, "__code__", None), "co_names", ()))
+    return all(hasattr(cls, a) or a in names for a in _V3PLUS_ATTRS) and not (hasattr(cls, "conv_seg") or "conv_seg" in names)
+
+
+def use_v3plus_forward(head_cls):
+    """Bind v3plus_forward on a Euclidean DeepLab-v3+ head class (the reference's DepthwiseSeparableASPP, or any nn.Module class
+    whose instances carry parallel_branches, global_branch, bottleneck, shortcut, decoder and old_decoder and no conv_seg).  Returns
+    the class; the forward it replaced is kept as `_unfused_forward`.  Idempotent."""
+    from .core.models.classifier import v3plus_forward
+    if not _is_v3plus_class(head_cls):
+        raise TypeError("use_v3plus_forward: %r is not a Euclidean DeepLab-v3+ head class (instances with %s and without conv_seg)"
+                        % (head_cls, ", ".join(_V3PLUS_ATTRS)))
+    if _inherited(head_cls, "forward") is v3plus_forward:
+        return head_cls
+    head_cls._unfused_forward = _inherited(head_cls, "forward")
+    head_cls.forward = v3plus_forward
+    return head_cls

@@ -478,6 +478,24 @@ int halo_masked_affine_relu_fwd(const float *x, const float *scale, const float 
 int halo_masked_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *mask, float *g_x, int64_t B, int64_t C,
                                 int64_t HW, void *stream);
 
+/* ---- frozen norm + ReLU + Dropout2d, both tensors kept: the Euclidean v3+ head's decoder[1], decoder[2] (halo_amd/norm.py) ----
+ *  The old decoder layout of DepthwiseSeparableASPP returns the tensor in front of its nn.Dropout2d and feeds the one behind it to
+ *  the classifier conv.  x, y, z, g_y, g_z, g_x (B, C, HW) f32 dense NCHW planes; scale, shift (C) f32; mask (B, C) f32 as above.
+ *    y   = relu(fl(fl(x scale[c]) + shift[c]))                       the first pair's statements, a NaN stays a NaN
+ *    z   = fl(y mask[b,c])                                           inf * 0 is the stock chain's NaN
+ *    g   = g_y,  fl(g_z mask[b,c])  or  fl(g_y + fl(g_z mask[b,c]))  the product first, then autograd's accumulation
+ *    g_x = fl((y <= 0 ? 0 : g) scale[c])                             a NaN y lets g through
+ *  bwd: g_y or g_z may be NULL (an output nobody used), not both; a NULL one is not read.  In a plane whose mask is 0 g_z is not
+ *  read and its term is taken as 0: with g_y NULL such a plane is written as zeros without reading y either.  A non-finite g_z in
+ *  a dropped plane therefore gives g_y's share alone where autograd gives a NaN; for finite gradients the bits are autograd's.
+ *  y and z must not overlap x or each other; g_x must not overlap g_y, g_z or y.  Routes, alignment rule and limits are those of
+ *  the pairs above.  HALO_E_ARG: an empty shape or a missing pointer; HALO_E_UNSUPPORTED: HW above 2^31 - 1025 or more than
+ *  2^31 - 1 workgroups. */
+int halo_dropout_pair_fwd(const float *x, const float *scale, const float *shift, const float *mask, float *y, float *z, int64_t B, int64_t C,
+                          int64_t HW, void *stream);
+int halo_dropout_pair_bwd(const float *g_y, const float *g_z, const float *y, const float *scale, const float *mask, float *g_x, int64_t B,
+                          int64_t C, int64_t HW, void *stream);
+
 /* ---- the image-pooling branch of the v3+ bottleneck folded into a border-aware bias (halo_amd/aspp.py) ----
  *  The bottleneck's 3x3 zero-padded conv reads Cx pyramid channels and Cg channels that are constant planes v[b,c] (the pooled branch,
  *  broadcast).  The constant planes' share of its output takes 9 values per (image, output channel): 3 row classes (0 top row, 1
