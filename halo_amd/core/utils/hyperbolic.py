@@ -204,8 +204,9 @@ def _pixel_contraction(D, X, chunk=512):
 def mlr_backward_terms(x, P, A, gout, c):
     """HyperMLR backward through the term maps: one HIP kernel for the reverse sweep (halo_hypermlr_bwd_terms) + the two dense
     contractions as library GEMMs (torch.einsum -> rocBLAS), W = [-P ; A/||A||], D = [dpx ; dxa].  Serves every shape; the
-    backward of _HyperMLRFn takes it where halo_hypermlr_backward does not serve the shape, and the tests use it as the
-    independent reference of that call.  x (B, C, H, W), P and A (O, C): float64, contiguous.  Returns (gx, gP, gA)."""
+    backward of _HyperMLRFn takes it where halo_hypermlr_backward does not serve the shape, and the tests compare that call with it
+    (another summation order, but the same k_mlr_prep and the same mlr_reverse sweep: the float64 CPU restatement in
+    tests/head_ref.py is what checks either).  x (B, C, H, W), P and A (O, C): float64, contiguous.  Returns (gx, gP, gA)."""
     dev = x.device
     B, Cc, H, W = x.shape
     O, hw = P.shape[0], H * W
