@@ -19,6 +19,7 @@
 // computes (AN_U x 16 bytes per operand in flight), lanes of a wave take consecutive groups.  The grid is planes x chunks in one
 // dimension; element offsets are 64-bit.  Chunks that lie wholly inside the plane take a branch without bounds tests.
 #include "halo_common.hpp"
+#include "halo_norm_dev.hpp"
 
 namespace halo {
 
@@ -27,28 +28,7 @@ constexpr int AN_U = 4;                        // groups per lane, all loaded be
 constexpr int AN_CHUNK = AN_TPB * AN_U;        // groups per workgroup
 enum { AN_NONE = 0, AN_PLAIN = 1, AN_AFFINE = 2 };
 
-typedef float an_f4 __attribute__((ext_vector_type(4)));
-
-template <int GW> __device__ __forceinline__ void an_load(const float *p, float *v)
-{
-    if constexpr (GW == 4) {
-        const an_f4 t = *reinterpret_cast<const an_f4 *>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-template <int GW> __device__ __forceinline__ void an_store(float *p, const float *v)
-{
-    if constexpr (GW == 4) {
-        an_f4 t;
-        t.x = v[0], t.y = v[1], t.z = v[2], t.w = v[3];
-        *reinterpret_cast<an_f4 *>(p) = t;
-    } else {
-        *p = v[0];
-    }
-}
+// an_f4, an_load, an_store, an_affine and an_relu live in halo_norm_dev.hpp (halo_maxpool.hip runs the same statements)
 
 struct AnGeom {
     int C;
@@ -76,15 +56,10 @@ __device__ __forceinline__ void an_fwd_chunk(const float *__restrict__ x, const 
             float out[GW];
 #pragma unroll
             for (int e = 0; e < GW; ++e) {
-                float s = xv[u][e] * sc;
-                s = s + sh;
+                float s = an_affine(xv[u][e], sc, sh);
                 if constexpr (RES == AN_PLAIN) s = s + rv[u][e];
-                if constexpr (RES == AN_AFFINE) {
-                    float id = rv[u][e] * rsc;
-                    id = id + rsh;
-                    s = s + id;
-                }
-                out[e] = s <= 0.0f ? 0.0f : s;
+                if constexpr (RES == AN_AFFINE) s = s + an_affine(rv[u][e], rsc, rsh);
+                out[e] = an_relu(s);
             }
             an_store<GW>(y + (size_t)g * GW, out);
         }

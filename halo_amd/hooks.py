@@ -445,12 +445,14 @@ def use_folded_image_pooling(head_cls):
 # With MODEL.FREEZE_BN every norm of the ResNet backbone and every dense norm of the heads is a FrozenBatchNorm2d whose forward is
 # torch statements (core/models/layers.py): a broadcast mul and a broadcast add over the activation, then an in-place ReLU, and at
 # the end of a residual block an in-place `out += identity` and another ReLU.  halo_amd.norm.norm_relu (halo_norm.hip) runs each
-# such chain as one pass with the chain's own roundings, so a hooked model returns the unhooked model's bits.  Two opt-in hooks,
-# neither bound by install():
+# such chain as one pass with the chain's own roundings, so a hooked model returns the unhooked model's bits.  Three opt-in hooks,
+# none bound by install():
 #   use_fused_frozen_norm(block_cls)   class level: the two residual blocks of core/models/resnet.py (Bottleneck, BasicBlock);
 #   fuse_norm_relu_pairs(module)       instance level: (FrozenBatchNorm2d, nn.ReLU) neighbours that a container calls in sequence --
 #                                      the stem inside the feature extractor's IntermediateLayerGetter, the v3+ heads'
 #                                      parallel_branches[0], global_branch, bottleneck and shortcut.
+#   fuse_norm_relu_pool(module)        instance level: (FrozenBatchNorm2d, nn.ReLU, nn.MaxPool2d(3, 2, 1)) neighbours, i.e. the stem with
+#                                      its pool, as halo_amd.norm.norm_relu_maxpool (halo_maxpool.hip); upgrades a fused pair.
 # The separable blocks' pointwise_bn + pointwise_activate, and the nn.Dropout2d behind the hyperbolic head's decoder[1], have hooks
 # of their own further down (use_fused_pointwise_norm, use_fused_decoder_dropout): they act on the second half of a block alone, so
 # they compose with use_fused_depthwise, whose first half is not bit-equal to the stock depthwise conv, without changing its bits.
@@ -565,6 +567,75 @@ def unfuse_norm_relu_pairs(module):
         if isinstance(f, (_PairNorm, _PairRelu)):
             del m.__dict__["forward"]
             n += isinstance(f, _PairNorm)
+    return n
+
+
+class _PoolNorm:
+    """the call of a norm whose next siblings are a ReLU and the stem's max-pool: pool(relu(norm(x))) in one pass"""
+
+    def __init__(self, norm, act, pool):
+        self.norm, self.act, self.pool = norm, act, pool
+
+    def __call__(self, x):
+        from .norm import fallback_reason, fused_norm_relu, fused_norm_relu_maxpool, pool_fallback_reason
+        norm, act, pool = self.norm, self.act, self.pool
+        if pool_fallback_reason(x, norm, pool) is None:
+            return fused_norm_relu_maxpool(x, norm)
+        if fallback_reason(x, norm) is None:               # turned away by the triple's speed rule alone: the pair's pass, then the pool
+            return type(pool).forward(pool, fused_norm_relu(x, norm))
+        return type(pool).forward(pool, type(act).forward(act, type(norm).forward(norm, x)))
+
+
+class _PoolPass:
+    """the call of the ReLU and of the pool behind such a norm: their input is already rectified and pooled"""
+
+    def __call__(self, x):
+        return x
+
+
+def fuse_norm_relu_pool(module):
+    """In the containers fuse_norm_relu_pairs walks, make each FrozenBatchNorm2d child whose next two siblings are an nn.ReLU and an
+    nn.MaxPool2d(3, 2, 1) (halo_amd.norm.pool_fallback_reason's pool) return halo_amd.norm.norm_relu_maxpool(x, norm, pool), and the
+    ReLU and the pool return their input: the backbone's stem.  All three get an instance-level `forward`; no module is added,
+    removed or renamed.  A (norm, ReLU) pair that fuse_norm_relu_pairs has fused is upgraded, and fuse_norm_relu_pairs afterwards
+    leaves the triple alone.  Left alone: an object that `module` holds in more than one place, a norm or a ReLU whose output the
+    container returns (IntermediateLayerGetter.return_layers; the pool's may be returned, it is the triple's), a foreign
+    instance-level `forward`.  A call the fused pass does not serve (a CPU tensor) runs the three stock forwards.  Returns the
+    number of triples fused (0 on a second call); unfuse_norm_relu_pool(module) undoes it."""
+    from .dwconv import _is_frozen
+    from .norm import _pool_reason
+    uses = {}
+    for m in module.modules():
+        for child in m._modules.values():
+            if child is not None:
+                uses[id(child)] = uses.get(id(child), 0) + 1
+    fused = 0
+    for box in _pair_containers(module):
+        kept = getattr(box, "return_layers", None) or {}
+        items = [(n, c) for n, c in box._modules.items() if c is not None]
+        for (name, norm), (act_name, act), (_, pool) in zip(items, items[1:], items[2:]):
+            if not _is_frozen(norm) or type(act) is not torch.nn.ReLU or _pool_reason(pool) is not None or name in kept or act_name in kept:
+                continue
+            if uses[id(norm)] != 1 or uses[id(act)] != 1 or uses[id(pool)] != 1 or "forward" in pool.__dict__:
+                continue
+            mine, theirs = norm.__dict__.get("forward"), act.__dict__.get("forward")
+            paired = isinstance(mine, _PairNorm) and isinstance(theirs, _PairRelu)
+            if not paired and (mine is not None or theirs is not None):
+                continue
+            norm.forward, act.forward, pool.forward = _PoolNorm(norm, act, pool), _PoolPass(), _PoolPass()
+            fused += 1
+    return fused
+
+
+def unfuse_norm_relu_pool(module):
+    """Undo fuse_norm_relu_pool(module): the three modules of every triple run their class's forward again.  Returns the number of
+    triples restored."""
+    n = 0
+    for m in module.modules():
+        f = m.__dict__.get("forward")
+        if isinstance(f, (_PoolNorm, _PoolPass)):
+            del m.__dict__["forward"]
+            n += isinstance(f, _PoolNorm)
     return n
 
 

@@ -29,6 +29,9 @@ cached.
 separable block and the dropout module behind it (the hyperbolic v3+ head's decoder[1], decoder[2]).
 `norm_relu_dropout2d_pair(x, bn, drop)` returns the tensor in front of the dropout as well (the Euclidean v3+ head's old decoder
 layout, which hands both on).
+
+`norm_relu_maxpool(x, bn, pool)` at the end is the backbone's stem behind its convolution: the norm, the ReLU and
+nn.MaxPool2d(3, 2, 1) in one pass each way (halo_maxpool.hip), which keeps one byte per output element for the backward.
 """
 import weakref
 
@@ -43,8 +46,9 @@ from .hfr import _autocast
 _BUFFERS = ("weight", "bias", "running_mean", "running_var")
 _cache = weakref.WeakKeyDictionary()          # norm module -> (the four keyed buffers, their versions, (scale, shift))
 # device launches issued by this module (tests count them): "fwd" / "bwd" of norm_relu, "masked_fwd" / "masked_bwd" of
-# norm_relu_dropout2d's own kernels, "pair_fwd" / "pair_bwd" of norm_relu_dropout2d_pair's
-launches = {"fwd": 0, "bwd": 0, "masked_fwd": 0, "masked_bwd": 0, "pair_fwd": 0, "pair_bwd": 0}
+# norm_relu_dropout2d's own kernels, "pair_fwd" / "pair_bwd" of norm_relu_dropout2d_pair's, "pool_fwd" / "pool_bwd" of
+# norm_relu_maxpool's ("pool_taps": the pool_fwd launches that kept the tap codes for a backward)
+launches = {"fwd": 0, "bwd": 0, "masked_fwd": 0, "masked_bwd": 0, "pair_fwd": 0, "pair_bwd": 0, "pool_fwd": 0, "pool_bwd": 0, "pool_taps": 0}
 # A speed rule, not a correctness rule (both sides return the same bits).  When a gradient will be asked for, a forward + backward
 # pair through the Python autograd node costs about 0.16 ms of host time whatever the size; measured alone, back to back, the stock
 # chain's pair is shorter than that below these element counts (2 x 512 x 80 x 160 loses without a residual_bn
@@ -356,5 +360,113 @@ def norm_relu_dropout2d_pair(x, bn, drop):
     return _NormReluDropPairFn.apply(x, scale, shift, noise)
 
 
+# ---------------------------------------------------------------- norm + ReLU + MaxPool2d(3, 2, 1): the stem
+# The stem of the backbone behind conv1 (core/models/resnet.py:191-195), on the largest activation of the network:
+#
+#     pool(F.relu(bn(x), inplace=True))                      pool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+#
+# norm_relu_maxpool reads x once and writes the pooled tensor and one byte per pooled element: the place of the recorded tap in
+# its window, or "blocked" when the ReLU let nothing through there.  The backward is a gather over those bytes and the incoming
+# gradient; neither the rectified tensor nor the pool's int64 indices exist.  The scan order, the tie and NaN rule and the
+# order of the backward's sums are ATen's (halo_maxpool.hip; tests/stem_pool_ref.py is the restatement).
+
+# norm_relu_maxpool's own speed rule, of the same kind as AUTOGRAD_MIN_ELEMENTS (a constant of its own: that dict is replaced
+# wholesale by its users): below this many elements an x that needs a gradient runs norm_relu and the stock pool.  Under autograd
+# all three chains sit on the host's cost of a pair of autograd nodes up to this size (at 2 x 64 x 160 x 320
+# the fused pair is ahead of norm_relu + pool in both runs, x1.05 and x2.00, and level with or ahead of the stock statements, x1.00
+# and x1.98; at 2 x 64 x 80 x 160 x1.03 and x1.54, x1.00 and x1.42, with the stock statements ahead in an earlier run), so the
+# threshold is the larger of the two small shapes timed; the stem's real shapes, 26 M elements and more, win x2.5 to x5.6.
+# Without a gradient every size is served.  Set it to 0 to serve every size.
+POOL_AUTOGRAD_MIN_ELEMENTS = 2 * 64 * 160 * 320
+
+
+def pool_statement(x, bn, pool):
+    """the stock statements: the stem's norm and in-place ReLU, then the pool module"""
+    return pool(F.relu(bn(x), inplace=True))
+
+
+def _pair_of(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _pool_reason(pool):
+    """why a pool module is not the stem's nn.MaxPool2d(3, 2, 1) (None: it is)"""
+    if type(pool) is not nn.MaxPool2d:
+        return "pool is not an nn.MaxPool2d"
+    for name, want in (("kernel_size", 3), ("stride", 2), ("padding", 1), ("dilation", 1)):
+        try:
+            got = _pair_of(getattr(pool, name))
+        except TypeError:
+            got = None
+        if got != (want, want):
+            return "the pool's %s is %r, not %d" % (name, getattr(pool, name), want)
+    if pool.ceil_mode:
+        return "the pool rounds its output size up (ceil_mode)"
+    if pool.return_indices:
+        return "the pool returns its indices"
+    return None
+
+
+def pool_fallback_reason(x, bn, pool):
+    """why norm_relu_maxpool(x, bn, pool) runs the torch statements (None: the fused pass serves it).  Reads no device memory."""
+    reason = _pool_reason(pool)
+    if reason is None:
+        reason = _envelope_reason(x, bn, None, None)
+    if reason is None and torch.is_grad_enabled() and getattr(x, "requires_grad", False) and x.numel() < POOL_AUTOGRAD_MIN_ELEMENTS:
+        return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (
+            x.numel(), POOL_AUTOGRAD_MIN_ELEMENTS)
+    return reason
+
+
+class _NormReluPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, keep):
+        B, C, H, W = x.shape
+        shape = (B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
+        out = x.new_empty(shape)
+        tap = torch.empty(shape, dtype=torch.uint8, device=x.device) if keep else None      # no backward will come: no codes
+        launches["pool_fwd"] += 1
+        launches["pool_taps"] += keep
+        _lib.check(_lib.lib().halo_maxpool_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(out), _lib.ptr(tap),
+                                                           B, C, H, W, _lib.stream_ptr(x.device)), "halo_maxpool_affine_relu_fwd")
+        if keep:
+            ctx.save_for_backward(tap, scale)
+        ctx.x_shape = (B, C, H, W)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gx = None
+        if ctx.needs_input_grad[0]:
+            tap, scale = ctx.saved_tensors
+            B, C, H, W = ctx.x_shape
+            g = g.to(device=tap.device, dtype=torch.float32).contiguous()
+            gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=tap.device)
+            launches["pool_bwd"] += 1
+            _lib.check(_lib.lib().halo_maxpool_affine_relu_bwd(_lib.ptr(g), _lib.ptr(tap), _lib.ptr(scale), _lib.ptr(gx), B, C, H, W,
+                                                               _lib.stream_ptr(tap.device)), "halo_maxpool_affine_relu_bwd")
+        return gx, None, None, None
+
+
+def norm_relu_maxpool(x, bn, pool):
+    """pool(relu(bn(x))) of a frozen norm and an nn.MaxPool2d(3, 2, 1), x (B, C, H, W): the stock chain's bits, forward and
+    backward.  Differentiable w.r.t. x; x is not modified; the backward keeps one byte per output element and scale, and the
+    forward writes those bytes only when a gradient for x will be asked for.  Outside the served envelope (pool_fallback_reason)
+    it returns pool_statement(x, bn, pool) -- except that an x the speed rule alone turns away runs norm_relu and the pool."""
+    if pool_fallback_reason(x, bn, pool) is not None:
+        if _pool_reason(pool) is None and fallback_reason(x, bn) is None:
+            return pool(fused_norm_relu(x, bn))
+        return pool_statement(x, bn, pool)
+    return fused_norm_relu_maxpool(x, bn)
+
+
+def fused_norm_relu_maxpool(x, bn):
+    """norm_relu_maxpool for arguments that pool_fallback_reason has accepted"""
+    scale, shift = cached_scale_shift(bn)
+    return _NormReluPoolFn.apply(x, scale, shift, bool(torch.is_grad_enabled() and x.requires_grad))
+
+
 __all__ = ["norm_relu", "torch_statement", "fallback_reason", "cached_scale_shift", "forget", "norm_relu_dropout2d",
-           "dropout_statement", "dropout_fallback_reason", "norm_relu_dropout2d_pair", "pair_statement", "pair_fallback_reason"]
+           "dropout_statement", "dropout_fallback_reason", "norm_relu_dropout2d_pair", "pair_statement", "pair_fallback_reason",
+           "norm_relu_maxpool", "pool_statement", "pool_fallback_reason"]

@@ -523,6 +523,25 @@ int halo_pool_fold_affine_relu_fwd(const float *z, const float *T, const float *
 int halo_pool_fold_affine_relu_bwd(const float *g, const float *y, const float *scale, float *g_z, double *g_T, int64_t B, int64_t Co,
                                    int64_t H, int64_t W, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- frozen norm + ReLU + 3x3 / stride 2 / padding 1 max-pool: the stem behind its convolution (halo_amd/norm.py) ----
+ *  x, g_x (B, C, H, W) f32 dense NCHW; out, g (B, C, OH, OW) f32 and tap (B, C, OH, OW) u8 dense, OH = (H - 1) / 2 + 1,
+ *  OW = (W - 1) / 2 + 1; scale, shift (C) f32.
+ *    z          = relu(fl(fl(x scale[c]) + shift[c]))               halo_affine_relu_fwd's statements and bits; never stored
+ *    out[oh,ow] = the recorded tap's z of the window of rows 2oh-1 .. 2oh+1 and columns 2ow-1 .. 2ow+1, taps inside the map only,
+ *                 scanned row-major from -inf, a tap taken if (v > max || isnan(v)): the first of equal values, the last NaN
+ *    tap[oh,ow] = 3 kh + kw of the recorded tap (its place in the window, 0..8), or 9 when its z <= 0 (no gradient passes)
+ *    g_x[h,w]   = fl(S scale[c]),  S = the f32 sum of g[oh,ow] over the windows whose tap names (h, w), ascending oh, then
+ *                 ascending ow, from +0: one to four terms, no atomics, the same bits on every call and every stream
+ *  The bits of `max_pool2d(relu_(x * scale + bias), 3, 2, 1)` and of the gather form of its autograd backward; a NaN z lets the
+ *  gradient through.  fwd: tap == NULL: the codes are not kept (no backward follows).  The backward reads g, tap and scale only.
+ *  out and tap must not overlap x; g_x must not overlap g or tap.  W % 4 == 0 with x and g_x 16-byte, out 8-byte and tap 2-byte
+ *  aligned runs 16-byte accesses of x and g_x, anything else one element per lane: same statements, same bits.  HALO_E_ARG: an
+ *  empty shape or a missing pointer; HALO_E_UNSUPPORTED: H W above 2^31 - 1025 or more than 2^31 - 1 workgroups. */
+int halo_maxpool_affine_relu_fwd(const float *x, const float *scale, const float *shift, float *out, uint8_t *tap, int64_t B, int64_t C,
+                                 int64_t H, int64_t W, void *stream);
+int halo_maxpool_affine_relu_bwd(const float *g, const uint8_t *tap, const float *scale, float *g_x, int64_t B, int64_t C, int64_t H,
+                                 int64_t W, void *stream);
+
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
 int halo_event_record(void *event, void *stream);
