@@ -62,6 +62,98 @@ def test_fullsize_fixture_equals_torch_cpu_chain(name):
     assert np.array_equal(ei.counts_from_pred(pred, label, 19), z["full_" + name + "/ref"].astype(np.int64))
 
 
+# ---------------------------------------------------------------- the contract chain (oracle/) and the ragged inputs
+@pytest.mark.parametrize("name", small_cases())
+def test_contract_chain_equals_the_reference_maps(name):
+    """eval.npz's `pred` is the reference's own arg-max map, so this makes the oracle's chain the reference's chain."""
+    z = np.load(FIX)
+    _, flip = (int(v) for v in z[name + "/meta"])
+    label = z[name + "/label"]
+    assert np.array_equal(ei.contract_pred(z[name + "/logits"], label.shape[-2:], bool(flip)), z[name + "/pred"])
+
+
+@pytest.mark.parametrize("name", sorted(ei.FULLSIZE))
+def test_contract_chain_reproduces_the_fullsize_digests(name):
+    z = np.load(FIX)
+    lg, label = ei.fullsize(name)
+    assert ei.digest(ei.contract_pred(lg, label.shape, True)[0]) == str(z["full_" + name + "/pred_sha256"])
+
+
+@pytest.mark.parametrize("name", sorted(ei.RAGGED))
+def test_contract_chain_differs_from_torch_only_within_atens_scalar_tails(name):
+    """Off multiples of 16 pixels torch's CPU softmax ends each thread's chunk with a scalar exp (tests/test_aten_exact.py:
+    fewer than 16 pixels per thread and softmaxed view, plus one vector for the chunk boundaries), so the live torch chain may
+    leave contract_pred there and nowhere else.  Observed: 0 pixels on every case but k19_identity_5x7, where the identity
+    resize spreads the NaN logit over four pixels (weight 0 times NaN) and torch's scalar tail orders a NaN maximum
+    differently: 2 of image 0's 35 pixels."""
+    K, views, lg, label, pred = ei.ragged_case(name)
+    live = ei.torch_chain_pred(torch.from_numpy(lg.copy()), label.shape[-2:], views == 2).numpy()
+    differ = (live != pred).reshape(pred.shape[0], -1).sum(1)
+    print(name, "pixels where torch's chain leaves the contract chain, per image:", differ.tolist())
+    assert int(differ.max()) <= views * 16 * (torch.get_num_threads() + 1)
+
+
+def test_ragged_inputs_reach_the_arms_they_are_meant_for():
+    from oracle import halo_oracle as ho
+    dtypes = {}
+    for name in sorted(ei.RAGGED):
+        _, K, (h, w), (H, W), views, B, dtype = ei.RAGGED[name]
+        K_, views_, lg, label, pred = ei.ragged_case(name)
+        assert (K_, views_) == (K, views) and lg.shape == (B * views, K, h, w) and label.shape == pred.shape == (B, H, W)
+        assert label.dtype == dtype and pred.dtype == np.int64 and pred.min() >= 0 and pred.max() < K
+        dtypes.setdefault("generic" if K not in (16, 19) else "k%d" % K, set()).add(np.dtype(dtype).name)
+        lab = label.astype(np.int64)
+        assert (lab == 255).any() and (dtype == np.uint8 or (lab == -1).any())
+        assert ((lab >= K) & (lab != 255)).any() or (K > 255 and dtype == np.uint8)
+        last = lab.reshape(B, -1)[:, -1]                                      # tail lanes recompute the last pixel: it must be one that
+        assert ((last >= 0) & (last < K) & (last != 255)).all()              # counts, or a lost lane mask would add nothing
+        counts = sum(ei.counts_from_pred(pred[i], label[i], K) for i in range(B))
+        assert counts[0].sum() > 0                                           # some agreement: the intersection row is not empty
+        one_cell = h * w == 1
+        if one_cell:
+            assert (pred == 3).all()                                         # one logit vector: identical planes 3 and 5, the lower wins
+        elif K > 1:
+            assert len(np.unique(pred)) >= 2
+        if not one_cell:
+            assert pred[ei.RAGGED_TIE_IMAGE % B, 0, 0] == 0                  # all classes tied in both views
+            i = ei.RAGGED_NAN_IMAGE % B
+            nan = np.isnan(ho.bilinear(lg[views * i, min(1, K - 1)], (H, W)))
+            assert nan.any() and (pred[i][nan] == 0).all()                   # NaN logit -> NaN softmax -> class 0
+        if K > 5:
+            planes = pred[ei.RAGGED_PLANES_IMAGE % B]
+            assert not (planes == 5).any()                                   # identical planes: never the higher index
+            if B > 1:                                                        # an image of its own: the planes win most of it
+                assert (planes == 3).sum() > 0.5 * planes.size               # (74 % where the identity size does no smoothing)
+        if K == 86:
+            # 3 K = 258 words: clear_hist / store_hist's second trip carries words 256 and 257, the targets of classes 84 and 85
+            assert counts[2, 84] > 0 and counts[2, 85] > 0
+        if K == 1024:
+            # the later trips carry every intersection word of a class >= 256 and all output and target words
+            assert (pred >= 256).any() and (lab[lab < K] >= 256).any() and counts[0, 256:].sum() > 0
+    assert all(v == {"int64", "int32", "uint8"} for v in dtypes.values()) and set(dtypes) == {"k19", "k16", "generic"}
+
+
+def test_counts_from_pred_with_an_ignore_index_among_the_classes_is_three_histc():
+    """intersectionAndUnionGPU (core/utils/misc.py:35-47) written out, with ignore_index = 7 < K: the label's 7s overwrite
+    the prediction and are then counted as class 7 in all three rows."""
+    K, ignore_index = 19, 7
+    _, _, _, label, pred = ei.ragged_case("k19_37x53")
+    for i in range(label.shape[0]):
+        output = torch.from_numpy(pred[i].copy()).view(-1)
+        target = torch.from_numpy(label[i].astype(np.int64)).view(-1)
+        assert (target == ignore_index).any() and ((output == ignore_index) & (target != ignore_index)).any()
+        output[target == ignore_index] = ignore_index                      # in place, before anything is counted
+
+        def histc(v):
+            return torch.histc(v.float(), bins=K, min=0, max=K - 1)
+
+        inter, out, tgt = histc(output[output == target]), histc(output), histc(target)
+        want = torch.stack([inter, out + tgt - inter, tgt]).numpy()
+        got = ei.counts_from_pred(pred[i], label[i], K, ignore_index=ignore_index)
+        assert np.array_equal(got, want.astype(np.int64))
+        assert not np.array_equal(got, ei.counts_from_pred(pred[i], label[i], K))
+
+
 def reference_epoch_end(inter, union, target):
     """train_learners.py:138-151 on gathered float32 per-image arrays (N, K)"""
     inter, union, target = inter.sum(axis=0), union.sum(axis=0), target.sum(axis=0)
