@@ -9,6 +9,9 @@
 //   gp  = y <= 0 ? 0 : g                                   a NaN y lets g through
 //   g_x = fl(gp * scale[c]);   g_r = gp   or   fl(gp * r_scale[c])
 //
+// halo_fork_affine_relu_bwd is the same backward for a y that two consumers read (the next block's conv1 and its identity):
+// g = fl(g_a + g_b), the one float32 add with which autograd accumulates two gradients, taken inside the pass.
+//
 // These are the statements and roundings of the torch chain `x * scale + bias; out += identity; relu_(out)` and of its autograd
 // backward, element by element, so the results are the chain's bits.  There is no sum over elements: no order to fix, no LDS, no
 // atomics, and the two routes below run the same statements.
@@ -83,16 +86,19 @@ __global__ void __launch_bounds__(AN_TPB) k_affine_relu_fwd(const float *__restr
     else an_fwd_chunk<GW, RES, false>(x + po, rp, y + po, g0, G.n, sc, sh, rsc, rsh);
 }
 
-template <int GW, bool GX, bool GR, bool RAFF, bool FULL>
-__device__ __forceinline__ void an_bwd_chunk(const float *__restrict__ g, const float *__restrict__ y, float *__restrict__ gx,
-                                             float *__restrict__ gr, int g0, int n, float sc, float rsc)
+// FORK: two gradients arrive at y (a block output that the next block reads twice); their sum is autograd's accumulation, one
+// float32 add, and the statements behind it are the same
+template <int GW, bool GX, bool GR, bool RAFF, bool FORK, bool FULL>
+__device__ __forceinline__ void an_bwd_chunk(const float *__restrict__ g, const float *__restrict__ g2, const float *__restrict__ y,
+                                             float *__restrict__ gx, float *__restrict__ gr, int g0, int n, float sc, float rsc)
 {
-    float gv[AN_U][GW], yv[AN_U][GW];
+    float gv[AN_U][GW], hv[AN_U][GW], yv[AN_U][GW];
 #pragma unroll
     for (int u = 0; u < AN_U; ++u) {
         const int q = g0 + u * AN_TPB;
         if (FULL || q < n) {
             an_load<GW>(g + (size_t)q * GW, gv[u]);
+            if constexpr (FORK) an_load<GW>(g2 + (size_t)q * GW, hv[u]);
             an_load<GW>(y + (size_t)q * GW, yv[u]);
         }
     }
@@ -103,7 +109,9 @@ __device__ __forceinline__ void an_bwd_chunk(const float *__restrict__ g, const 
             float ox[GW], orr[GW];
 #pragma unroll
             for (int e = 0; e < GW; ++e) {
-                const float gp = yv[u][e] <= 0.0f ? 0.0f : gv[u][e];
+                float gs = gv[u][e];
+                if constexpr (FORK) gs = gs + hv[u][e];
+                const float gp = yv[u][e] <= 0.0f ? 0.0f : gs;
                 ox[e] = gp * sc;
                 orr[e] = RAFF ? gp * rsc : gp;
             }
@@ -113,8 +121,8 @@ __device__ __forceinline__ void an_bwd_chunk(const float *__restrict__ g, const 
     }
 }
 
-template <int GW, bool GX, bool GR, bool RAFF>
-__global__ void __launch_bounds__(AN_TPB) k_affine_relu_bwd(const float *__restrict__ g, const float *__restrict__ y,
+template <int GW, bool GX, bool GR, bool RAFF, bool FORK>
+__global__ void __launch_bounds__(AN_TPB) k_affine_relu_bwd(const float *__restrict__ g, const float *__restrict__ g2, const float *__restrict__ y,
                                                             const float *__restrict__ scale, const float *__restrict__ r_scale,
                                                             float *__restrict__ gx, float *__restrict__ gr, AnGeom G)
 {
@@ -122,10 +130,11 @@ __global__ void __launch_bounds__(AN_TPB) k_affine_relu_bwd(const float *__restr
     const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
     const size_t po = (size_t)plane * G.n * GW;
     const float sc = GX ? scale[c] : 0.0f, rsc = RAFF ? r_scale[c] : 0.0f;
+    const float *hp = FORK ? g2 + po : nullptr;
     float *xp = GX ? gx + po : nullptr, *rp = GR ? gr + po : nullptr;
     const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.n - base >= AN_CHUNK) an_bwd_chunk<GW, GX, GR, RAFF, true>(g + po, y + po, xp, rp, g0, G.n, sc, rsc);
-    else an_bwd_chunk<GW, GX, GR, RAFF, false>(g + po, y + po, xp, rp, g0, G.n, sc, rsc);
+    if (G.n - base >= AN_CHUNK) an_bwd_chunk<GW, GX, GR, RAFF, FORK, true>(g + po, hp, y + po, xp, rp, g0, G.n, sc, rsc);
+    else an_bwd_chunk<GW, GX, GR, RAFF, FORK, false>(g + po, hp, y + po, xp, rp, g0, G.n, sc, rsc);
 }
 
 static int an_plan(const char *who, int64_t B, int64_t C, int64_t HW, bool vec, AnGeom &G, unsigned &grid)
@@ -156,16 +165,16 @@ static void an_launch_fwd(int res, unsigned grid, hipStream_t st, const float *x
     else hipLaunchKernelGGL((k_affine_relu_fwd<GW, AN_AFFINE>), g, b, 0, st, x, scale, shift, r, r_scale, r_shift, y, G);
 }
 
-template <int GW>
-static void an_launch_bwd(bool want_x, bool want_r, bool raff, unsigned grid, hipStream_t st, const float *g, const float *y,
+template <int GW, bool FORK>
+static void an_launch_bwd(bool want_x, bool want_r, bool raff, unsigned grid, hipStream_t st, const float *g, const float *g2, const float *y,
                           const float *scale, const float *r_scale, float *gx, float *gr, const AnGeom &G)
 {
     const dim3 gd(grid), b(AN_TPB);
-    if (want_x && !want_r) hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, false, false>), gd, b, 0, st, g, y, scale, r_scale, gx, gr, G);
-    else if (!want_x && !raff) hipLaunchKernelGGL((k_affine_relu_bwd<GW, false, true, false>), gd, b, 0, st, g, y, scale, r_scale, gx, gr, G);
-    else if (!want_x) hipLaunchKernelGGL((k_affine_relu_bwd<GW, false, true, true>), gd, b, 0, st, g, y, scale, r_scale, gx, gr, G);
-    else if (!raff) hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, false>), gd, b, 0, st, g, y, scale, r_scale, gx, gr, G);
-    else hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, true>), gd, b, 0, st, g, y, scale, r_scale, gx, gr, G);
+    if (want_x && !want_r) hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, false, false, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
+    else if (!want_x && !raff) hipLaunchKernelGGL((k_affine_relu_bwd<GW, false, true, false, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
+    else if (!want_x) hipLaunchKernelGGL((k_affine_relu_bwd<GW, false, true, true, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
+    else if (!raff) hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, false, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
+    else hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, true, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
 }
 
 
@@ -635,21 +644,42 @@ extern "C" int halo_affine_relu_fwd(const float *x, const float *scale, const fl
     return check_launch(who);
 }
 
+// both entries of the block tail's backward: g_b is the second gradient of halo_fork_affine_relu_bwd, null for the single one
+static int an_bwd_entry(const char *who, const float *g, const float *g_b, const float *y, const float *scale, const float *r_scale, float *g_x,
+                        float *g_r, int64_t B, int64_t C, int64_t HW, void *stream)
+{
+    if (!g_x && !g_r) return fail(HALO_E_ARG, "%s: neither g_x nor g_r is asked for", who);
+    if (g_x && !scale) return fail(HALO_E_ARG, "%s: g_x needs scale", who);
+    const bool vec = an_vec(HW, g, y, g_x, g_r) && (uintptr_t)g_b % 16 == 0;
+    AnGeom G;
+    unsigned grid;
+    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
+    const bool raff = g_r && r_scale, wx = g_x != nullptr, wr = g_r != nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (g_b) {
+        if (vec) an_launch_bwd<4, true>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
+        else an_launch_bwd<1, true>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
+    } else {
+        if (vec) an_launch_bwd<4, false>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
+        else an_launch_bwd<1, false>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
+    }
+    return check_launch(who);
+}
+
 extern "C" int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *r_scale, float *g_x, float *g_r,
                                     int64_t B, int64_t C, int64_t HW, void *stream)
 {
     const char *who = "halo_affine_relu_bwd";
     if (!g || !y) return fail(HALO_E_ARG, "%s: null argument", who);
-    if (!g_x && !g_r) return fail(HALO_E_ARG, "%s: neither g_x nor g_r is asked for", who);
-    if (g_x && !scale) return fail(HALO_E_ARG, "%s: g_x needs scale", who);
-    const bool vec = an_vec(HW, g, y, g_x, g_r);
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    const bool raff = g_r && r_scale;
-    if (vec) an_launch_bwd<4>(g_x != nullptr, g_r != nullptr, raff, grid, (hipStream_t)stream, g, y, scale, r_scale, g_x, g_r, G);
-    else an_launch_bwd<1>(g_x != nullptr, g_r != nullptr, raff, grid, (hipStream_t)stream, g, y, scale, r_scale, g_x, g_r, G);
-    return check_launch(who);
+    return an_bwd_entry(who, g, nullptr, y, scale, r_scale, g_x, g_r, B, C, HW, stream);
+}
+
+extern "C" int halo_fork_affine_relu_bwd(const float *g_a, const float *g_b, const float *y, const float *scale, const float *r_scale,
+                                         float *g_x, float *g_r, int64_t B, int64_t C, int64_t HW, void *stream)
+{
+    const char *who = "halo_fork_affine_relu_bwd";
+    if (!g_a || !g_b || !y) return fail(HALO_E_ARG, "%s: null argument", who);
+    return an_bwd_entry(who, g_a, g_b, y, scale, r_scale, g_x, g_r, B, C, HW, stream);
 }
 
 extern "C" int halo_masked_affine_relu_fwd(const float *x, const float *scale, const float *shift, const float *mask, float *y, int64_t B,

@@ -445,9 +445,11 @@ def use_folded_image_pooling(head_cls):
 # With MODEL.FREEZE_BN every norm of the ResNet backbone and every dense norm of the heads is a FrozenBatchNorm2d whose forward is
 # torch statements (core/models/layers.py): a broadcast mul and a broadcast add over the activation, then an in-place ReLU, and at
 # the end of a residual block an in-place `out += identity` and another ReLU.  halo_amd.norm.norm_relu (halo_norm.hip) runs each
-# such chain as one pass with the chain's own roundings, so a hooked model returns the unhooked model's bits.  Three opt-in hooks,
+# such chain as one pass with the chain's own roundings, so a hooked model returns the unhooked model's bits.  Four opt-in hooks,
 # none bound by install():
 #   use_fused_frozen_norm(block_cls)   class level: the two residual blocks of core/models/resnet.py (Bottleneck, BasicBlock);
+#   fuse_residual_chains(module)       instance level: the nn.Sequential layers of such blocks; a block output that the next block
+#                                      reads twice takes its two gradients in the tail's own backward pass (norm_relu_fork);
 #   fuse_norm_relu_pairs(module)       instance level: (FrozenBatchNorm2d, nn.ReLU) neighbours that a container calls in sequence --
 #                                      the stem inside the feature extractor's IntermediateLayerGetter, the v3+ heads'
 #                                      parallel_branches[0], global_branch, bottleneck and shortcut.
@@ -460,10 +462,14 @@ def use_folded_image_pooling(head_cls):
 _RESIDUAL_ATTRS = ("conv1", "bn1", "conv2", "bn2", "relu", "downsample")
 
 
-def fused_residual_forward(self, x):
-    from .norm import norm_relu
+def residual_body(self, x, identity, fork):
+    """a residual block on input x with `identity` as what a block without a downsample adds (x itself, or the second tensor of a
+    forked predecessor: the same values); returns (y, y_id), the output twice -- halo_amd.norm.norm_relu_fork's pair when `fork`,
+    the same tensor object otherwise"""
+    from .norm import norm_relu, norm_relu_fork
     if type(self.relu) is not torch.nn.ReLU:
-        return self._unfused_forward(x)
+        y = self._unfused_forward(x)
+        return y, y
     out = norm_relu(self.conv1(x), self.bn1)
     if getattr(self, "conv3", None) is not None:             # the Bottleneck form
         out = norm_relu(self.conv2(out), self.bn2)
@@ -472,10 +478,19 @@ def fused_residual_forward(self, x):
         out, last = self.conv2(out), self.bn2
     down = self.downsample
     if down is None:
-        return norm_relu(out, last, residual=x)
-    if type(down) is torch.nn.Sequential and len(down) == 2 and isinstance(down[0], torch.nn.Conv2d):
-        return norm_relu(out, last, residual=down[0](x), residual_bn=down[1])      # the downsample norm is folded into the pass
-    return norm_relu(out, last, residual=down(x))
+        residual, residual_bn = identity, None
+    elif type(down) is torch.nn.Sequential and len(down) == 2 and isinstance(down[0], torch.nn.Conv2d):
+        residual, residual_bn = down[0](x), down[1]          # the downsample norm is folded into the pass
+    else:
+        residual, residual_bn = down(x), None
+    if fork:
+        return norm_relu_fork(out, last, residual=residual, residual_bn=residual_bn)
+    y = norm_relu(out, last, residual=residual, residual_bn=residual_bn)
+    return y, y
+
+
+def fused_residual_forward(self, x):
+    return residual_body(self, x, x, False)[0]
 
 
 def _is_residual_class(cls):
@@ -503,6 +518,77 @@ def use_fused_frozen_norm(block_cls):
     block_cls._unfused_forward = _inherited(block_cls, "forward")
     block_cls.forward = fused_residual_forward
     return block_cls
+
+
+def _forks_into(block):
+    """a block in front of `block` may hand it a forked output: it reads its input as conv1(x) and as the identity"""
+    return block.downsample is None and type(block.relu) is torch.nn.ReLU
+
+
+class _ChainWalk:
+    """the call of an nn.Sequential of bound residual blocks: block i + 1 reads block i's output twice, as conv1's input and as its
+    identity, so block i returns it twice from one autograd node (halo_amd.norm.norm_relu_fork) and both gradients arrive at that
+    node's backward, which adds them in its own pass"""
+
+    def __init__(self, box):
+        self.box = box
+
+    def __call__(self, x):
+        from torch.nn.modules import module as M
+        box = self.box
+        blocks = list(box._modules.values())
+        hooked = any(b._forward_hooks or b._forward_pre_hooks for b in blocks) or bool(
+            getattr(M, "_global_forward_hooks", None) or getattr(M, "_global_forward_pre_hooks", None))
+        if hooked or not _chain_blocks(box):                 # hooks fire in __call__, which the walk does not go through
+            return torch.nn.Sequential.forward(box, x)
+        identity = x
+        for i, block in enumerate(blocks):
+            fork = type(block.relu) is torch.nn.ReLU and i + 1 < len(blocks) and _forks_into(blocks[i + 1])
+            x, identity = residual_body(block, x, identity, fork)
+        return x
+
+
+def _chain_blocks(box):
+    """the children of a container that fuse_residual_chains serves (None: it does not): two or more, every one of a class bound by
+    use_fused_frozen_norm, none with an instance-level forward"""
+    blocks = list(box._modules.values())
+    if len(blocks) < 2:
+        return None
+    for b in blocks:
+        if b is None or getattr(type(b), "forward", None) is not fused_residual_forward or "forward" in b.__dict__:
+            return None
+    return blocks
+
+
+def fuse_residual_chains(module):
+    """Give every nn.Sequential under `module` (itself included) that holds two or more residual blocks, all of classes bound by
+    use_fused_frozen_norm, and nothing else, an instance-level `forward` that walks its blocks: a block whose successor has no
+    downsample (and an nn.ReLU) ends in halo_amd.norm.norm_relu_fork, the successor runs conv1 on one of the two tensors and adds the
+    other, and the two gradients that come back are added inside the first block's tail backward instead of by a kernel of the
+    engine's.  A block in front of a downsample, and the last block, end in norm_relu as before.  Outputs and gradients are the
+    unchained model's bits.  No module is added, removed or renamed: state_dict() and named_modules() are unchanged.  A container
+    that already carries an instance-level `forward`, or whose children do not qualify, is left alone.
+
+    The walk calls the blocks' bodies, not their `__call__`: while any block of a container carries a forward hook or a forward
+    pre-hook (or a global module forward hook is registered), or its children have changed so that they no longer qualify, a call of
+    that container runs nn.Sequential.forward, blocks, hooks and all, without the chaining.  Returns the number of containers bound
+    (0 on a second call); unfuse_residual_chains(module) undoes it."""
+    n = 0
+    for box in module.modules():
+        if isinstance(box, torch.nn.Sequential) and "forward" not in box.__dict__ and _chain_blocks(box) is not None:
+            box.forward = _ChainWalk(box)
+            n += 1
+    return n
+
+
+def unfuse_residual_chains(module):
+    """Undo fuse_residual_chains(module).  Returns the number of containers restored."""
+    n = 0
+    for m in module.modules():
+        if isinstance(m.__dict__.get("forward"), _ChainWalk):
+            del m.__dict__["forward"]
+            n += 1
+    return n
 
 
 class _PairNorm:

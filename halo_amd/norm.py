@@ -25,6 +25,9 @@ version is one through a detached alias (`bn.weight.data.mul_()`, or a write thr
 inference mode); call `forget(bn)` after such a write.  A buffer without a version counter (an inference-mode tensor) is never
 cached.
 
+`norm_relu_fork(x, bn, residual, residual_bn)` is norm_relu for a result that two consumers read (a block output inside a ResNet
+layer): it returns the tensor twice from one autograd node, whose backward adds the two arriving gradients inside its own pass.
+
 `norm_relu_dropout2d(x, bn, drop)` further down is the same pass with nn.Dropout2d's per-plane multiplier folded in: the tail of a
 separable block and the dropout module behind it (the hyperbolic v3+ head's decoder[1], decoder[2]).
 `norm_relu_dropout2d_pair(x, bn, drop)` returns the tensor in front of the dropout as well (the Euclidean v3+ head's old decoder
@@ -47,8 +50,9 @@ _BUFFERS = ("weight", "bias", "running_mean", "running_var")
 _cache = weakref.WeakKeyDictionary()          # norm module -> (the four keyed buffers, their versions, (scale, shift))
 # device launches issued by this module (tests count them): "fwd" / "bwd" of norm_relu, "masked_fwd" / "masked_bwd" of
 # norm_relu_dropout2d's own kernels, "pair_fwd" / "pair_bwd" of norm_relu_dropout2d_pair's, "pool_fwd" / "pool_bwd" of
-# norm_relu_maxpool's ("pool_taps": the pool_fwd launches that kept the tap codes for a backward)
-launches = {"fwd": 0, "bwd": 0, "masked_fwd": 0, "masked_bwd": 0, "pair_fwd": 0, "pair_bwd": 0, "pool_fwd": 0, "pool_bwd": 0, "pool_taps": 0}
+# norm_relu_maxpool's ("pool_taps": the pool_fwd launches that kept the tap codes for a backward), "fork_bwd" of norm_relu_fork's
+# two-gradient backward (its forward and its one-gradient backward are norm_relu's launches and count as "fwd" / "bwd")
+launches = {"fwd": 0, "bwd": 0, "fork_bwd": 0, "masked_fwd": 0, "masked_bwd": 0, "pair_fwd": 0, "pair_bwd": 0, "pool_fwd": 0, "pool_bwd": 0, "pool_taps": 0}
 # A speed rule, not a correctness rule (both sides return the same bits).  When a gradient will be asked for, a forward + backward
 # pair through the Python autograd node costs about 0.16 ms of host time whatever the size; measured alone, back to back, the stock
 # chain's pair is shorter than that below these element counts (2 x 512 x 80 x 160 loses without a residual_bn
@@ -194,6 +198,92 @@ def fused_norm_relu(x, bn, residual=None, residual_bn=None):
     if residual_bn is not None:
         r_scale, r_shift = cached_scale_shift(residual_bn)
     return _NormReluFn.apply(x, scale, shift, residual, r_scale, r_shift)
+
+
+# ---------------------------------------------------------------- a block tail whose output is read twice
+# Inside a ResNet layer the output y of block k is read twice by block k + 1: by its conv1 and as its identity.  In the backward
+# two gradients arrive at y, conv1's data gradient and the g_r of block k + 1's tail, and the engine adds them with a stand-alone
+# kernel before block k's tail backward reads the sum.  norm_relu_fork returns y twice, as (y, a view of y), from one autograd node
+# with two outputs, so both gradients reach its backward, which adds them inside the pass (halo_fork_affine_relu_bwd): one float32
+# add per element, autograd's accumulation and its bits, whichever gradient came first.
+
+# norm_relu_fork's own speed rule, of the same kind as AUTOGRAD_MIN_ELEMENTS (a constant of its own: that dict is replaced
+# wholesale by its users, and tests read it): with fewer elements than this a tensor that needs a gradient goes through norm_relu
+# and its rule, and the engine adds the two gradients as before.  It is the smallest block output timed: in a
+# chain of three bottlenecks the two forked tails of 2 x 512 x 80 x 160 are ahead of the parent configuration, which leaves them
+# to the stock statements, in both runs, so from this size on the fork is served in every variant -- also where "plain" above is
+# larger; 2 x 256 x 160 x 320, 2 x 1024 x 80 x 160 and 2 x 2048 x 80 x 160 win as well.  Nothing smaller was measured.  Set it to 0
+# to serve every size.
+FORK_AUTOGRAD_MIN_ELEMENTS = 2 * 512 * 80 * 160
+
+
+def fork_fallback_reason(x, bn, residual=None, residual_bn=None):
+    """why norm_relu_fork(x, bn, residual, residual_bn) hands on norm_relu's tensor twice (None: its own two-output node serves
+    it).  The envelope is norm_relu's; the size rule is FORK_AUTOGRAD_MIN_ELEMENTS.  Reads no device memory."""
+    reason = _envelope_reason(x, bn, residual, residual_bn)
+    if reason is not None:
+        return reason
+    if not (torch.is_grad_enabled() and (getattr(x, "requires_grad", False) or getattr(residual, "requires_grad", False))):
+        return "no gradient will be asked for"
+    if x.numel() < FORK_AUTOGRAD_MIN_ELEMENTS:
+        return "%d elements are fewer than the %d from which the two-gradient backward was measured faster" % (
+            x.numel(), FORK_AUTOGRAD_MIN_ELEMENTS)
+    return None
+
+
+class _NormReluForkFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, r, r_scale, r_shift):
+        B, C, H, W = x.shape
+        y = torch.empty_like(x)
+        launches["fwd"] += 1
+        _lib.check(_lib.lib().halo_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(r), _lib.ptr(r_scale),
+                                                   _lib.ptr(r_shift), _lib.ptr(y), B, C, H * W, _lib.stream_ptr(x.device)),
+                   "halo_affine_relu_fwd")
+        ctx.save_for_backward(y, scale, r_scale)
+        ctx.set_materialize_grads(False)                   # an output nobody used arrives as None and is not read
+        return y, y.view_as(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_a, g_b):
+        y, scale, r_scale = ctx.saved_tensors
+        B, C, H, W = y.shape
+        want_x, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        gx = gr = None
+        if (want_x or want_r) and (g_a is not None or g_b is not None):
+            g_a, g_b = (None if g is None else g.to(device=y.device, dtype=torch.float32).contiguous() for g in (g_a, g_b))
+            gx = torch.empty_like(y) if want_x else None
+            gr = torch.empty_like(y) if want_r else None
+            if g_a is not None and g_b is not None:
+                launches["fork_bwd"] += 1
+                _lib.check(_lib.lib().halo_fork_affine_relu_bwd(_lib.ptr(g_a), _lib.ptr(g_b), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(r_scale),
+                                                                _lib.ptr(gx), _lib.ptr(gr), B, C, H * W, _lib.stream_ptr(y.device)),
+                           "halo_fork_affine_relu_bwd")
+            else:
+                g = g_a if g_a is not None else g_b
+                launches["bwd"] += 1
+                _lib.check(_lib.lib().halo_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(r_scale), _lib.ptr(gx),
+                                                           _lib.ptr(gr), B, C, H * W, _lib.stream_ptr(y.device)), "halo_affine_relu_bwd")
+        return gx, None, None, gr, None, None
+
+
+def norm_relu_fork(x, bn, residual=None, residual_bn=None):
+    """norm_relu(x, bn, residual, residual_bn) for a result that two consumers read: returns (y, y_id), the same values twice,
+    y_id a view of y.  Hand one to each consumer and write in place to neither.  When both send a gradient back, the backward adds
+    the two inside its one pass (the engine's accumulation: one float32 add, the stock chain's bits); when one does, it is
+    norm_relu's backward; when none does, or no input needs a gradient, nothing is launched.  Outside norm_relu's envelope, where
+    no gradient will be asked for, and below FORK_AUTOGRAD_MIN_ELEMENTS (fork_fallback_reason) it returns the same tensor object
+    twice, t = norm_relu(x, bn, residual, residual_bn) -- torch_statement's result wherever norm_relu runs the stock statements --
+    and autograd does what it does without this operator."""
+    if fork_fallback_reason(x, bn, residual, residual_bn) is not None:
+        t = norm_relu(x, bn, residual, residual_bn)
+        return t, t
+    scale, shift = cached_scale_shift(bn)
+    r_scale = r_shift = None
+    if residual_bn is not None:
+        r_scale, r_shift = cached_scale_shift(residual_bn)
+    return _NormReluForkFn.apply(x, scale, shift, residual, r_scale, r_shift)
 
 
 # ---------------------------------------------------------------- norm + ReLU + Dropout2d
@@ -467,6 +557,6 @@ def fused_norm_relu_maxpool(x, bn):
     return _NormReluPoolFn.apply(x, scale, shift, bool(torch.is_grad_enabled() and x.requires_grad))
 
 
-__all__ = ["norm_relu", "torch_statement", "fallback_reason", "cached_scale_shift", "forget", "norm_relu_dropout2d",
+__all__ = ["norm_relu", "norm_relu_fork", "fork_fallback_reason", "torch_statement", "fallback_reason", "cached_scale_shift", "forget", "norm_relu_dropout2d",
            "dropout_statement", "dropout_fallback_reason", "norm_relu_dropout2d_pair", "pair_statement", "pair_fallback_reason",
            "norm_relu_maxpool", "pool_statement", "pool_fallback_reason"]

@@ -462,6 +462,12 @@ int halo_affine_relu_fwd(const float *x, const float *scale, const float *shift,
                          float *y, int64_t B, int64_t C, int64_t HW, void *stream);
 int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *r_scale, float *g_x, float *g_r, int64_t B,
                          int64_t C, int64_t HW, void *stream);
+/*  The same backward for a y that two consumers read (a block output: the next block's conv1 and its identity), so that two
+ *  gradients g_a, g_b (B, C, HW) arrive at it:  g = fl(g_a + g_b), the one float32 add of autograd's accumulation, then the
+ *  statements above on that g.  g_x and g_r must not overlap g_a, g_b or y; the 16-byte route needs g_b aligned as well.  Checks
+ *  and limits are those of the single-gradient entry; a NULL g_a or g_b is HALO_E_ARG. */
+int halo_fork_affine_relu_bwd(const float *g_a, const float *g_b, const float *y, const float *scale, const float *r_scale, float *g_x,
+                              float *g_r, int64_t B, int64_t C, int64_t HW, void *stream);
 
 /* ---- frozen norm + ReLU + Dropout2d: the pointwise tail of a separable block and the dropout behind it (halo_amd/norm.py) ----
  *  x, y, g, g_x (B, C, HW) f32 dense NCHW planes; scale, shift (C) f32; mask (B, C) f32: the multiplier of plane (b, c), 0 or
