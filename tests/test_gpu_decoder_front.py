@@ -8,16 +8,26 @@ tests/test_gpu_dwconv.py (u = 2^-24) against the three stock modules evaluated i
 
   forward  15u (|scale| sum_k |w_k| |x_k| + |bias| + |running_mean scale|), the ReLU mask equal outside the band |pre_64| <= bound
   g_x      15u |scale| sum_k |w_k| |g mask| with the device's mask;  g_w  8u sum |gp| |x| per tap
+  g_a      (small cases) A^T g_x[:, :Ca] with A^T the resize backward in float64 over the float32 taps (adjoint64 of
+           tests/resize_ref.py, held to the float32 adjoint in tests/test_dwconv_geometry_host.py): the bound is the propagated
+           error of g_up, A^T bx, plus the resize backward's own 2 (n + 8) u A^T(|g_x| + bx) of tests/test_gpu_resize.py
+
+The synthetic cases of tests/dwconv_cases.py are drawn on the CPU and copied: tests/test_dwconv_geometry_host.py proves what each
+reaches of the work split and of DwUpSrc's source-row reuse, and that at most 1e-4 of their elements lie within 4 x the forward
+bound of zero -- the cap on the band that is asserted for them here.
 """
 import gc
 import types
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import dwconv_cases as K
 import dwconv_ref as R
+import resize_ref as Z
 
 pytestmark = pytest.mark.gpu
 U = R.U
@@ -29,6 +39,8 @@ CASES = {
     "single_cell": ((2, 2, 1, 1), (2, 1, 8, 8)),                # in_size = 1: both taps coincide
     "identity": ((1, 2, 6, 8), (1, 2, 6, 8)),                   # h = H, w = W
 }
+SYNTHETIC = {"syn_" + name: shapes for name, (shapes, _) in K.DECODER.items()}
+ALL = dict(CASES, **SYNTHETIC)
 HEAD = ((2, 512, 80, 160), (2, 48, 160, 320))
 
 
@@ -64,6 +76,14 @@ def operands(shapes, dev, seed=0):
     return a, s, g, conv, bn
 
 
+def synthetic_operands(name, dev):
+    """a synthetic case's operands, drawn on the CPU by tests/dwconv_cases.py and copied"""
+    c = K.decoder(name)
+    conv, bn = R.modules(c, dev)
+    a, s, g = (torch.from_numpy(c[k]).to(dev) for k in ("a", "s", "g"))
+    return a, s, g, conv, bn
+
+
 def fused(a, s, g, conv, bn):
     from halo_amd.dwconv import upcat_fallback_reason, upsample_cat_depthwise_bn_relu
     assert upcat_fallback_reason(a, s, conv, bn) is None
@@ -89,7 +109,10 @@ _small = {}
 def small(name, dev):
     """(operands, the composition's y, g_a, g_s, g_w) of a small case: computed once, shared, never written"""
     if name not in _small:
-        ops = operands(CASES[name], dev, seed=len(_small) + 1)
+        if name in SYNTHETIC:
+            ops = synthetic_operands(name[4:], dev)
+        else:
+            ops = operands(CASES[name], dev, seed=sorted(CASES).index(name) + 1)
         _small[name] = (ops, composition(*ops))
     return _small[name]
 
@@ -108,11 +131,11 @@ def offset_view(t):
     return v
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
+@pytest.mark.parametrize("name", sorted(CASES) + list(SYNTHETIC))
 def test_bits_of_the_composition(dev, name):
     ops, want = small(name, dev)
     y = want[0]
-    Ca = CASES[name][0][1]
+    Ca = ALL[name][0][1]
     dead = (y == 0).all(dim=3).all(dim=2).all(dim=0)
     assert bool(dead[Ca - 1]) and not bool(dead[:Ca].all()) and not bool(dead[Ca:].all())     # a dead channel, live ones from a and from s
     assert_same_bits(fused(*ops), want)
@@ -132,10 +155,11 @@ def test_unaligned_operands_take_the_one_column_route_with_the_same_bits(dev):
     assert_same_bits(fused(a.transpose(2, 3).contiguous().transpose(2, 3), wide[..., ::2], g, conv, bn), want)
 
 
-def against_float64(a, s, g, conv, bn, got):
-    """y, g_s and g_w against the stock modules in float64 over x_ref (float32, the device resize's own values)"""
+def against_float64(a, s, g, conv, bn, got, band_cap=None, g_a=False):
+    """y, g_s and g_w against the stock modules in float64 over x_ref (float32, the device resize's own values); g_a against the
+    float64 adjoint of the resize applied to the float64 data gradient, on the CPU"""
     from halo_amd.resize import bilinear_resize
-    y, _, gs, gw = got
+    y, ga, gs, gw = got
     Ca, (B, C, H, W) = a.shape[1], y.shape
     v = lambda t: t.double().reshape(1, C, 1, 1)
     with torch.no_grad():
@@ -151,6 +175,8 @@ def against_float64(a, s, g, conv, bn, got):
         assert bool((err <= bound).all())
         band = pre.abs() <= bound
         print(tuple(y.shape), "band fraction", float(band.double().mean()))
+        if band_cap is not None:
+            assert float(band.double().mean()) <= band_cap
         mask = y > 0
         assert bool(((mask == (pre > 0)) | band).all())
         del pre, err, band, bound
@@ -162,6 +188,15 @@ def against_float64(a, s, g, conv, bn, got):
         ex = (gs.double() - rx[:, Ca:]).abs()
         print(tuple(y.shape), "g_s: max err / bound", float((ex / bx[:, Ca:].clamp(min=1e-300)).max()))
         assert bool((ex <= bx[:, Ca:]).all())
+        if g_a:
+            (h, w), u = a.shape[2:], 2.0 ** -24
+            r, b = rx[:, :Ca].cpu().numpy(), bx[:, :Ca].cpu().numpy()
+            want = Z.adjoint64(r, h, w)
+            ba = Z.adjoint64(b, h, w) + 2 * (Z.terms_bound(h, w, H, W) + 8) * u * Z.adjoint64(np.abs(r) + b, h, w)
+            ea = np.abs(ga.cpu().numpy().astype(np.float64) - want)
+            print(tuple(y.shape), "g_a: max err / bound", float((ea / np.maximum(ba, 1e-300)).max()))
+            assert (ea <= ba).all()
+            assert (ea[ba == 0] == 0).all() and (ba[:, Ca - 1] == 0).all()     # the dead a-channel: exactly 0
         del rx, bx, ex, gm
         xp = F.pad(x, (1, 1, 1, 1))
         rw, bw = torch.zeros(C, 9, dtype=torch.float64, device=y.device), torch.zeros(C, 9, dtype=torch.float64, device=y.device)
@@ -176,7 +211,13 @@ def against_float64(a, s, g, conv, bn, got):
 
 def test_small_case_against_float64(dev):
     ops, _ = small("vector_two_bands", dev)
-    against_float64(*ops, fused(*ops))
+    against_float64(*ops, fused(*ops), g_a=True)
+
+
+@pytest.mark.parametrize("name", sorted(set(CASES) - {"vector_two_bands"}) + list(SYNTHETIC))
+def test_every_other_small_case_against_float64(dev, name):
+    ops, _ = small(name, dev)
+    against_float64(*ops, fused(*ops), band_cap=1e-4 if name in SYNTHETIC else None, g_a=True)
 
 
 def test_head_shape_bits_and_float64(dev):

@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from resize_ref import make_taps, numpy_adjoint, scale_of, terms_bound, weights
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOL = "halo_bilinear_upsample_bwd"
 
@@ -145,54 +147,6 @@ def test_unmarked_tail_keeps_todays_training_statements():
 
 
 # ---------------------------------------------------------------- the yardstick: numpy adjoint from make_taps
-def make_taps(o, scale, n_in, T):
-    """halo_softmax.hpp make_taps in dtype T"""
-    f = T(scale) * T(o)
-    i0 = min(int(f), n_in - 1)
-    i1 = i0 + (1 if i0 < n_in - 1 else 0)
-    l1 = T(f - T(i0))
-    return i0, i1, T(T(1) - l1), l1
-
-
-def scale_of(n_in, n_out, T):
-    return T(n_in - 1) / T(n_out - 1) if n_out > 1 else T(0)
-
-
-def weights(n_in, n_out, T):
-    """(n_out, n_in): row o holds the weights of output coordinate o (both taps add where they coincide)"""
-    A = np.zeros((n_out, n_in), dtype=T)
-    s = scale_of(n_in, n_out, T)
-    for o in range(n_out):
-        i0, i1, l0, l1 = make_taps(o, s, n_in, T)
-        A[o, i0] = T(A[o, i0] + l0)
-        A[o, i1] = T(A[o, i1] + l1)
-    return A
-
-
-def numpy_adjoint(g, h, w):
-    """grad_in[p, i, j] = sum_Y sum_X wy(Y, i) wx(X, j) g[p, Y, X] in g's dtype, ascending X inside a row, rows in ascending Y"""
-    T = g.dtype.type
-    P, H, W = g.shape
-    Ay, Ax = weights(h, H, T), weights(w, W, T)
-    out = np.zeros((P, h, w), dtype=T)
-    for i in range(h):
-        ys = np.nonzero(Ay[:, i])[0]
-        for j in range(w):
-            xs = np.nonzero(Ax[:, j])[0]
-            acc = np.zeros(P, dtype=T)
-            for Y in ys:
-                r = np.zeros(P, dtype=T)
-                for X in xs:
-                    r = (r + Ax[X, j] * g[:, Y, X]).astype(T)
-                acc = (acc + Ay[Y, i] * r).astype(T)
-            out[:, i, j] = acc
-    return out
-
-
-def terms_bound(h, w, H, W):
-    return (2 * math.ceil((H - 1) / max(h - 1, 1)) + 1) * (2 * math.ceil((W - 1) / max(w - 1, 1)) + 1)
-
-
 def cpu_adjoint(g, h, w):
     t = torch.from_numpy(g)
     x = torch.zeros((1, g.shape[0], h, w), dtype=t.dtype, requires_grad=True)
