@@ -16,11 +16,15 @@
 // backward, element by element, so the results are the chain's bits.  There is no sum over elements: no order to fix, no LDS, no
 // atomics, and the two routes below run the same statements.
 //
-// Tiling: a workgroup works inside one plane, so scale, shift, r_scale and r_shift are block-uniform scalar loads.  A plane of
-// HW elements is cut into chunks of AN_TPB * AN_U groups of GW elements (GW = 4: 16-byte loads and stores, HW % 4 == 0 and
-// every operand 16-byte aligned; GW = 1: any HW and any alignment).  A lane issues its AN_U loads of every operand before it
-// computes (AN_U x 16 bytes per operand in flight), lanes of a wave take consecutive groups.  The grid is planes x chunks in one
-// dimension; element offsets are 64-bit.  Chunks that lie wholly inside the plane take a branch without bounds tests.
+// Tiling, the same for every pass of this file (an_place, an_walk): a workgroup works inside one plane, so scale, shift, r_scale,
+// r_shift and a plane's mask or table are block-uniform scalar loads.  A plane of HW elements is cut into chunks of AN_TPB * AN_U
+// groups of GW elements (GW = 4: 16-byte loads and stores, HW % 4 == 0 and every operand 16-byte aligned; GW = 1: any HW and any
+// alignment).  A lane issues its AN_U loads of every operand before it computes (AN_U x 16 bytes per operand in flight), lanes of
+// a wave take consecutive groups.  The grid is planes x chunks in one dimension; element offsets are 64-bit.  Chunks that lie
+// wholly inside the plane take a branch without bounds tests.  What a pass computes is its op: a struct that says which of the
+// walk's operands it reads and writes, holds the block-uniform scalars, and turns one loaded group into one group to store.
+#include <type_traits>
+
 #include "halo_common.hpp"
 #include "halo_norm_dev.hpp"
 
@@ -39,35 +43,80 @@ struct AnGeom {
     int cpp;      // chunks per plane
 };
 
-template <int GW, int RES, bool FULL>
-__device__ __forceinline__ void an_fwd_chunk(const float *__restrict__ x, const float *__restrict__ r, float *__restrict__ y, int g0, int n,
-                                             float sc, float sh, float rsc, float rsh)
+// where a workgroup and its lane work: one chunk of one plane
+struct AnPlace {
+    unsigned plane;   // b * C + c: indexes what there is one of per plane (the dropout mask, the fold table)
+    int c;            // the channel: indexes scale, shift, r_scale, r_shift
+    size_t po;        // the plane's element offset in every activation operand
+    int g0;           // the lane's first group; its other AN_U - 1 follow at strides of AN_TPB
+    int n;            // groups per plane
+    bool full;        // the chunk lies wholly inside the plane
+};
+
+template <int GW> __device__ __forceinline__ AnPlace an_place(const AnGeom &G)
 {
-    float xv[AN_U][GW], rv[AN_U][GW];
+    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
+    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), base = chunk * AN_CHUNK;
+    return {plane, (int)(plane % (unsigned)G.C), (size_t)plane * G.n * GW, base + (int)threadIdx.x, G.n, G.n - base >= AN_CHUNK};
+}
+
+// One chunk.  An op has
+//   IN[3], OUT[2]                      which of i0..i2 it reads and of o0, o1 it writes; the others may be null and are not touched
+//   group<GW>(g, in, out)              in[k][e] -> out[k][e] for the GW elements of group g of the plane (element g * GW + e), one
+//                                      rounding per statement; per-lane state that outlives the walk sits behind a pointer in the op
+// All loads of all AN_U groups are issued before the first group() runs.  An op that reads nothing issues no load.  The operands
+// stay separate __restrict__ parameters down to the loads, and the registers are laid out operand by operand: group by group
+// (in[u][k]) the one-element route takes 4 to 6 more VGPRs in every kernel.
+template <int GW, bool FULL, class Op>
+__device__ __forceinline__ void an_chunk(Op &op, const AnPlace &P, const float *__restrict__ i0, const float *__restrict__ i1,
+                                         const float *__restrict__ i2, float *__restrict__ o0, float *__restrict__ o1)
+{
+    float in[3][AN_U][GW];
 #pragma unroll
     for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) {
-            an_load<GW>(x + (size_t)g * GW, xv[u]);
-            if constexpr (RES != AN_NONE) an_load<GW>(r + (size_t)g * GW, rv[u]);
+        const int g = P.g0 + u * AN_TPB;
+        if (FULL || g < P.n) {
+            if constexpr (Op::IN[0]) an_load<GW>(i0 + P.po + (size_t)g * GW, in[0][u]);
+            if constexpr (Op::IN[1]) an_load<GW>(i1 + P.po + (size_t)g * GW, in[1][u]);
+            if constexpr (Op::IN[2]) an_load<GW>(i2 + P.po + (size_t)g * GW, in[2][u]);
         }
     }
 #pragma unroll
     for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) {
-            float out[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                float s = an_affine(xv[u][e], sc, sh);
-                if constexpr (RES == AN_PLAIN) s = s + rv[u][e];
-                if constexpr (RES == AN_AFFINE) s = s + an_affine(rv[u][e], rsc, rsh);
-                out[e] = an_relu(s);
-            }
-            an_store<GW>(y + (size_t)g * GW, out);
+        const int g = P.g0 + u * AN_TPB;
+        if (FULL || g < P.n) {
+            float out[2][GW];
+            const float *const v[3] = {in[0][u], in[1][u], in[2][u]};
+            op.template group<GW>(g, v, out);
+            if constexpr (Op::OUT[0]) an_store<GW>(o0 + P.po + (size_t)g * GW, out[0]);
+            if constexpr (Op::OUT[1]) an_store<GW>(o1 + P.po + (size_t)g * GW, out[1]);
         }
     }
 }
+
+template <int GW, class Op>
+__device__ __forceinline__ void an_walk(Op &op, const AnPlace &P, const float *__restrict__ i0, const float *__restrict__ i1,
+                                        const float *__restrict__ i2, float *__restrict__ o0, float *__restrict__ o1)
+{
+    if (P.full) an_chunk<GW, true>(op, P, i0, i1, i2, o0, o1);
+    else an_chunk<GW, false>(op, P, i0, i1, i2, o0, o1);
+}
+
+// in: x, r  out: y
+template <int RES> struct AnFwd {
+    static constexpr bool IN[3] = {true, RES != AN_NONE, false}, OUT[2] = {true, false};
+    float sc, sh, rsc, rsh;
+    template <int GW> __device__ __forceinline__ void group(int, const float *const *in, float (*out)[GW]) const
+    {
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            float s = an_affine(in[0][e], sc, sh);
+            if constexpr (RES == AN_PLAIN) s = s + in[1][e];
+            if constexpr (RES == AN_AFFINE) s = s + an_affine(in[1][e], rsc, rsh);
+            out[0][e] = an_relu(s);
+        }
+    }
+};
 
 template <int GW, int RES>
 __global__ void __launch_bounds__(AN_TPB) k_affine_relu_fwd(const float *__restrict__ x, const float *__restrict__ scale,
@@ -75,66 +124,37 @@ __global__ void __launch_bounds__(AN_TPB) k_affine_relu_fwd(const float *__restr
                                                             const float *__restrict__ r_scale, const float *__restrict__ r_shift,
                                                             float *__restrict__ y, AnGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
-    const size_t po = (size_t)plane * G.n * GW;
-    const float sc = scale[c], sh = shift[c];
-    const float rsc = RES == AN_AFFINE ? r_scale[c] : 0.0f, rsh = RES == AN_AFFINE ? r_shift[c] : 0.0f;
-    const float *rp = RES != AN_NONE ? r + po : nullptr;
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.n - base >= AN_CHUNK) an_fwd_chunk<GW, RES, true>(x + po, rp, y + po, g0, G.n, sc, sh, rsc, rsh);
-    else an_fwd_chunk<GW, RES, false>(x + po, rp, y + po, g0, G.n, sc, sh, rsc, rsh);
+    const AnPlace P = an_place<GW>(G);
+    AnFwd<RES> op{scale[P.c], shift[P.c], RES == AN_AFFINE ? r_scale[P.c] : 0.0f, RES == AN_AFFINE ? r_shift[P.c] : 0.0f};
+    an_walk<GW>(op, P, x, r, nullptr, y, nullptr);
 }
 
-// FORK: two gradients arrive at y (a block output that the next block reads twice); their sum is autograd's accumulation, one
-// float32 add, and the statements behind it are the same
-template <int GW, bool GX, bool GR, bool RAFF, bool FORK, bool FULL>
-__device__ __forceinline__ void an_bwd_chunk(const float *__restrict__ g, const float *__restrict__ g2, const float *__restrict__ y,
-                                             float *__restrict__ gx, float *__restrict__ gr, int g0, int n, float sc, float rsc)
-{
-    float gv[AN_U][GW], hv[AN_U][GW], yv[AN_U][GW];
+// in: g, g2, y  out: g_x, g_r.  FORK: two gradients arrive at y (a block output that the next block reads twice); their sum is
+// autograd's accumulation, one float32 add, and the statements behind it are the same
+template <bool GX, bool GR, bool RAFF, bool FORK> struct AnBwd {
+    static constexpr bool IN[3] = {true, FORK, true}, OUT[2] = {GX, GR};
+    float sc, rsc;
+    template <int GW> __device__ __forceinline__ void group(int, const float *const *in, float (*out)[GW]) const
+    {
 #pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int q = g0 + u * AN_TPB;
-        if (FULL || q < n) {
-            an_load<GW>(g + (size_t)q * GW, gv[u]);
-            if constexpr (FORK) an_load<GW>(g2 + (size_t)q * GW, hv[u]);
-            an_load<GW>(y + (size_t)q * GW, yv[u]);
+        for (int e = 0; e < GW; ++e) {
+            float gs = in[0][e];
+            if constexpr (FORK) gs = gs + in[1][e];
+            const float gp = in[2][e] <= 0.0f ? 0.0f : gs;
+            out[0][e] = gp * sc;
+            out[1][e] = RAFF ? gp * rsc : gp;
         }
     }
-#pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int q = g0 + u * AN_TPB;
-        if (FULL || q < n) {
-            float ox[GW], orr[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                float gs = gv[u][e];
-                if constexpr (FORK) gs = gs + hv[u][e];
-                const float gp = yv[u][e] <= 0.0f ? 0.0f : gs;
-                ox[e] = gp * sc;
-                orr[e] = RAFF ? gp * rsc : gp;
-            }
-            if constexpr (GX) an_store<GW>(gx + (size_t)q * GW, ox);
-            if constexpr (GR) an_store<GW>(gr + (size_t)q * GW, orr);
-        }
-    }
-}
+};
 
 template <int GW, bool GX, bool GR, bool RAFF, bool FORK>
 __global__ void __launch_bounds__(AN_TPB) k_affine_relu_bwd(const float *__restrict__ g, const float *__restrict__ g2, const float *__restrict__ y,
                                                             const float *__restrict__ scale, const float *__restrict__ r_scale,
                                                             float *__restrict__ gx, float *__restrict__ gr, AnGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
-    const size_t po = (size_t)plane * G.n * GW;
-    const float sc = GX ? scale[c] : 0.0f, rsc = RAFF ? r_scale[c] : 0.0f;
-    const float *hp = FORK ? g2 + po : nullptr;
-    float *xp = GX ? gx + po : nullptr, *rp = GR ? gr + po : nullptr;
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.n - base >= AN_CHUNK) an_bwd_chunk<GW, GX, GR, RAFF, FORK, true>(g + po, hp, y + po, xp, rp, g0, G.n, sc, rsc);
-    else an_bwd_chunk<GW, GX, GR, RAFF, FORK, false>(g + po, hp, y + po, xp, rp, g0, G.n, sc, rsc);
+    const AnPlace P = an_place<GW>(G);
+    AnBwd<GX, GR, RAFF, FORK> op{GX ? scale[P.c] : 0.0f, RAFF ? r_scale[P.c] : 0.0f};
+    an_walk<GW>(op, P, g, g2, y, gx, gr);
 }
 
 static int an_plan(const char *who, int64_t B, int64_t C, int64_t HW, bool vec, AnGeom &G, unsigned &grid)
@@ -155,26 +175,31 @@ static bool an_vec(int64_t HW, const void *p0, const void *p1, const void *p2, c
     return HW % 4 == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3) % 16) == 0;
 }
 
-template <int GW>
-static void an_launch_fwd(int res, unsigned grid, hipStream_t st, const float *x, const float *scale, const float *shift, const float *r,
-                          const float *r_scale, const float *r_shift, float *y, const AnGeom &G)
+// the route as a type: launch(std::integral_constant<int, GW>) with GW = 4 for the 16-byte route, 1 for the one-element route
+template <class L> static void an_route(bool vec, L launch)
 {
-    const dim3 g(grid), b(AN_TPB);
-    if (res == AN_NONE) hipLaunchKernelGGL((k_affine_relu_fwd<GW, AN_NONE>), g, b, 0, st, x, scale, shift, r, r_scale, r_shift, y, G);
-    else if (res == AN_PLAIN) hipLaunchKernelGGL((k_affine_relu_fwd<GW, AN_PLAIN>), g, b, 0, st, x, scale, shift, r, r_scale, r_shift, y, G);
-    else hipLaunchKernelGGL((k_affine_relu_fwd<GW, AN_AFFINE>), g, b, 0, st, x, scale, shift, r, r_scale, r_shift, y, G);
+    if (vec) launch(std::integral_constant<int, 4>());
+    else launch(std::integral_constant<int, 1>());
 }
 
-template <int GW, bool FORK>
-static void an_launch_bwd(bool want_x, bool want_r, bool raff, unsigned grid, hipStream_t st, const float *g, const float *g2, const float *y,
-                          const float *scale, const float *r_scale, float *gx, float *gr, const AnGeom &G)
+// run-time flags as types: f(std::bool_constant<flag>...), in the order given.  An entry rules out the combinations it cannot
+// reach with `if constexpr`, so that no kernel is built for them.
+template <class F> static void an_flags(F f) { f(); }
+template <class F, class... Rest> static void an_flags(F f, bool flag, Rest... rest)
 {
-    const dim3 gd(grid), b(AN_TPB);
-    if (want_x && !want_r) hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, false, false, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
-    else if (!want_x && !raff) hipLaunchKernelGGL((k_affine_relu_bwd<GW, false, true, false, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
-    else if (!want_x) hipLaunchKernelGGL((k_affine_relu_bwd<GW, false, true, true, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
-    else if (!raff) hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, false, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
-    else hipLaunchKernelGGL((k_affine_relu_bwd<GW, true, true, true, FORK>), gd, b, 0, st, g, g2, y, scale, r_scale, gx, gr, G);
+    if (flag) an_flags([&](auto... more) { f(std::true_type(), more...); }, rest...);
+    else an_flags([&](auto... more) { f(std::false_type(), more...); }, rest...);
+}
+
+// an entry behind its null checks: plans the walk of B x C planes of HW elements on the route `vec`, has launch(GW, G, grid) enqueue
+// the kernel, and reports
+template <class L> static int an_run(const char *who, int64_t B, int64_t C, int64_t HW, bool vec, L launch)
+{
+    AnGeom G;
+    unsigned grid;
+    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
+    an_route(vec, [&](auto GW) { launch(GW, G, dim3(grid)); });
+    return check_launch(who);
 }
 
 
@@ -189,98 +214,64 @@ static void an_launch_bwd(bool want_x, bool want_r, bool raff, unsigned grid, hi
 // or NaN and either branch gives a zero for a finite g: such a plane's workgroups write zeros and read neither g nor y.  That is
 // the one deviation from autograd, which computes fl(fl(g * 0) * scale) there: a NaN for a non-finite g.
 
-template <int GW, bool FULL>
-__device__ __forceinline__ void an_mask_fwd_chunk(const float *__restrict__ x, float *__restrict__ y, int g0, int n, float sc, float sh, float m)
-{
-    float xv[AN_U][GW];
+// in: x  out: y
+struct AnMaskFwd {
+    static constexpr bool IN[3] = {true, false, false}, OUT[2] = {true, false};
+    float sc, sh, m;
+    template <int GW> __device__ __forceinline__ void group(int, const float *const *in, float (*out)[GW]) const
+    {
 #pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) an_load<GW>(x + (size_t)g * GW, xv[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) {
-            float out[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                float s = xv[u][e] * sc;
-                s = s + sh;
-                s = s <= 0.0f ? 0.0f : s;
-                out[e] = s * m;
-            }
-            an_store<GW>(y + (size_t)g * GW, out);
+        for (int e = 0; e < GW; ++e) {
+            float s = in[0][e] * sc;
+            s = s + sh;
+            s = s <= 0.0f ? 0.0f : s;
+            out[0][e] = s * m;
         }
     }
-}
+};
 
 template <int GW>
 __global__ void __launch_bounds__(AN_TPB) k_affine_relu_mask_fwd(const float *__restrict__ x, const float *__restrict__ scale,
                                                                  const float *__restrict__ shift, const float *__restrict__ mask,
                                                                  float *__restrict__ y, AnGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
-    const size_t po = (size_t)plane * G.n * GW;
-    const float sc = scale[c], sh = shift[c], m = mask[plane];
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.n - base >= AN_CHUNK) an_mask_fwd_chunk<GW, true>(x + po, y + po, g0, G.n, sc, sh, m);
-    else an_mask_fwd_chunk<GW, false>(x + po, y + po, g0, G.n, sc, sh, m);
+    const AnPlace P = an_place<GW>(G);
+    AnMaskFwd op{scale[P.c], shift[P.c], mask[P.plane]};
+    an_walk<GW>(op, P, x, nullptr, nullptr, y, nullptr);
 }
 
-template <int GW, bool KEPT, bool FULL>
-__device__ __forceinline__ void an_mask_bwd_chunk(const float *__restrict__ g, const float *__restrict__ y, float *__restrict__ gx, int g0, int n,
-                                                  float sc, float m)
-{
-    float gv[AN_U][GW], yv[AN_U][GW];
-    if constexpr (KEPT) {
+// in: g, y  out: g_x.  KEPT = false, a dropped plane: reads nothing, writes zeros
+template <bool KEPT> struct AnMaskBwd {
+    static constexpr bool IN[3] = {KEPT, KEPT, false}, OUT[2] = {true, false};
+    float sc, m;
+    template <int GW> __device__ __forceinline__ void group(int, const float *const *in, float (*out)[GW]) const
+    {
 #pragma unroll
-        for (int u = 0; u < AN_U; ++u) {
-            const int q = g0 + u * AN_TPB;
-            if (FULL || q < n) {
-                an_load<GW>(g + (size_t)q * GW, gv[u]);
-                an_load<GW>(y + (size_t)q * GW, yv[u]);
+        for (int e = 0; e < GW; ++e) {
+            if constexpr (KEPT) {
+                float t = in[0][e] * m;
+                t = t * sc;
+                out[0][e] = in[1][e] <= 0.0f ? 0.0f : t;
+            } else {
+                out[0][e] = 0.0f;
             }
         }
     }
-#pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int q = g0 + u * AN_TPB;
-        if (FULL || q < n) {
-            float ox[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                if constexpr (KEPT) {
-                    float t = gv[u][e] * m;
-                    t = t * sc;
-                    ox[e] = yv[u][e] <= 0.0f ? 0.0f : t;
-                } else {
-                    ox[e] = 0.0f;
-                }
-            }
-            an_store<GW>(gx + (size_t)q * GW, ox);
-        }
-    }
-}
+};
 
 template <int GW>
 __global__ void __launch_bounds__(AN_TPB) k_affine_relu_mask_bwd(const float *__restrict__ g, const float *__restrict__ y,
                                                                  const float *__restrict__ scale, const float *__restrict__ mask,
                                                                  float *__restrict__ gx, AnGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
-    const size_t po = (size_t)plane * G.n * GW;
-    const float sc = scale[c], m = mask[plane];
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    const bool full = G.n - base >= AN_CHUNK;
+    const AnPlace P = an_place<GW>(G);
+    const float sc = scale[P.c], m = mask[P.plane];
     if (m != 0.0f) {                                             // block-uniform: the whole workgroup lies in one plane
-        if (full) an_mask_bwd_chunk<GW, true, true>(g + po, y + po, gx + po, g0, G.n, sc, m);
-        else an_mask_bwd_chunk<GW, true, false>(g + po, y + po, gx + po, g0, G.n, sc, m);
+        AnMaskBwd<true> op{sc, m};
+        an_walk<GW>(op, P, g, y, nullptr, gx, nullptr);
     } else {
-        if (full) an_mask_bwd_chunk<GW, false, true>(g + po, y + po, gx + po, g0, G.n, sc, m);
-        else an_mask_bwd_chunk<GW, false, false>(g + po, y + po, gx + po, g0, G.n, sc, m);
+        AnMaskBwd<false> op{sc, m};
+        an_walk<GW>(op, P, g, y, nullptr, gx, nullptr);
     }
 }
 
@@ -298,120 +289,71 @@ __global__ void __launch_bounds__(AN_TPB) k_affine_relu_mask_bwd(const float *__
 // is taken as 0, which it is for a finite g_z (autograd has a NaN for a non-finite one: section 18's deviation).  With g_y absent
 // such a plane's workgroups write zeros and read nothing.
 
-template <int GW, bool FULL>
-__device__ __forceinline__ void an_pair_fwd_chunk(const float *__restrict__ x, float *__restrict__ y, float *__restrict__ z, int g0, int n,
-                                                  float sc, float sh, float m)
-{
-    float xv[AN_U][GW];
+// in: x  out: y, z
+struct AnPairFwd {
+    static constexpr bool IN[3] = {true, false, false}, OUT[2] = {true, true};
+    float sc, sh, m;
+    template <int GW> __device__ __forceinline__ void group(int, const float *const *in, float (*out)[GW]) const
+    {
 #pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) an_load<GW>(x + (size_t)g * GW, xv[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) {
-            float oy[GW], oz[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                float s = xv[u][e] * sc;
-                s = s + sh;
-                oy[e] = s <= 0.0f ? 0.0f : s;
-                oz[e] = oy[e] * m;
-            }
-            an_store<GW>(y + (size_t)g * GW, oy);
-            an_store<GW>(z + (size_t)g * GW, oz);
+        for (int e = 0; e < GW; ++e) {
+            float s = in[0][e] * sc;
+            s = s + sh;
+            out[0][e] = s <= 0.0f ? 0.0f : s;
+            out[1][e] = out[0][e] * m;
         }
     }
-}
+};
 
 template <int GW>
 __global__ void __launch_bounds__(AN_TPB) k_affine_relu_pair_fwd(const float *__restrict__ x, const float *__restrict__ scale,
                                                                  const float *__restrict__ shift, const float *__restrict__ mask,
                                                                  float *__restrict__ y, float *__restrict__ z, AnGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
-    const size_t po = (size_t)plane * G.n * GW;
-    const float sc = scale[c], sh = shift[c], m = mask[plane];
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.n - base >= AN_CHUNK) an_pair_fwd_chunk<GW, true>(x + po, y + po, z + po, g0, G.n, sc, sh, m);
-    else an_pair_fwd_chunk<GW, false>(x + po, y + po, z + po, g0, G.n, sc, sh, m);
+    const AnPlace P = an_place<GW>(G);
+    AnPairFwd op{scale[P.c], shift[P.c], mask[P.plane]};
+    an_walk<GW>(op, P, x, nullptr, nullptr, y, z);
 }
 
-// GY / GZ: which of the two gradients this workgroup reads (neither: it writes zeros)
-template <int GW, bool GY, bool GZ, bool FULL>
-__device__ __forceinline__ void an_pair_bwd_chunk(const float *__restrict__ gy, const float *__restrict__ gz, const float *__restrict__ y,
-                                                  float *__restrict__ gx, int g0, int n, float sc, float m)
-{
-    float av[AN_U][GW], bv[AN_U][GW], yv[AN_U][GW];
-    if constexpr (GY || GZ) {
+// in: g_y, g_z, y  out: g_x.  GY / GZ: which of the two gradients this workgroup reads (neither: it reads nothing and writes zeros)
+template <bool GY, bool GZ> struct AnPairBwd {
+    static constexpr bool IN[3] = {GY, GZ, GY || GZ}, OUT[2] = {true, false};
+    float sc, m;
+    template <int GW> __device__ __forceinline__ void group(int, const float *const *in, float (*out)[GW]) const
+    {
 #pragma unroll
-        for (int u = 0; u < AN_U; ++u) {
-            const int q = g0 + u * AN_TPB;
-            if (FULL || q < n) {
-                if constexpr (GY) an_load<GW>(gy + (size_t)q * GW, av[u]);
-                if constexpr (GZ) an_load<GW>(gz + (size_t)q * GW, bv[u]);
-                an_load<GW>(y + (size_t)q * GW, yv[u]);
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int q = g0 + u * AN_TPB;
-        if (FULL || q < n) {
-            float ox[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                if constexpr (GY || GZ) {
-                    float t;
-                    if constexpr (GZ) {
-                        t = bv[u][e] * m;
-                        if constexpr (GY) t = av[u][e] + t;
-                    } else {
-                        t = av[u][e];
-                    }
-                    t = yv[u][e] <= 0.0f ? 0.0f : t;
-                    ox[e] = t * sc;
+        for (int e = 0; e < GW; ++e) {
+            if constexpr (GY || GZ) {
+                float t;
+                if constexpr (GZ) {
+                    t = in[1][e] * m;
+                    if constexpr (GY) t = in[0][e] + t;
                 } else {
-                    ox[e] = 0.0f;
+                    t = in[0][e];
                 }
+                t = in[2][e] <= 0.0f ? 0.0f : t;
+                out[0][e] = t * sc;
+            } else {
+                out[0][e] = 0.0f;
             }
-            an_store<GW>(gx + (size_t)q * GW, ox);
         }
     }
-}
+};
 
 template <int GW, bool GY, bool GZ>
 __global__ void __launch_bounds__(AN_TPB) k_affine_relu_pair_bwd(const float *__restrict__ gy, const float *__restrict__ gz,
                                                                  const float *__restrict__ y, const float *__restrict__ scale,
                                                                  const float *__restrict__ mask, float *__restrict__ gx, AnGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.cpp;         // 32-bit: the grid has at most 2^31 - 1 workgroups
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.cpp), c = (int)(plane % (unsigned)G.C);
-    const size_t po = (size_t)plane * G.n * GW;
-    const float sc = scale[c], m = GZ ? mask[plane] : 1.0f;
-    const float *ap = GY ? gy + po : nullptr, *bp = GZ ? gz + po : nullptr;
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    const bool full = G.n - base >= AN_CHUNK;
+    const AnPlace P = an_place<GW>(G);
+    const float sc = scale[P.c], m = GZ ? mask[P.plane] : 1.0f;
     if (!GZ || m != 0.0f) {                                      // block-uniform: the whole workgroup lies in one plane
-        if (full) an_pair_bwd_chunk<GW, GY, GZ, true>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
-        else an_pair_bwd_chunk<GW, GY, GZ, false>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
+        AnPairBwd<GY, GZ> op{sc, m};
+        an_walk<GW>(op, P, gy, gz, y, gx, nullptr);
     } else {                                                     // a dropped plane: g_z's term is 0
-        if (full) an_pair_bwd_chunk<GW, GY, false, true>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
-        else an_pair_bwd_chunk<GW, GY, false, false>(ap, bp, y + po, gx + po, g0, G.n, sc, m);
+        AnPairBwd<GY, false> op{sc, m};
+        an_walk<GW>(op, P, gy, gz, y, gx, nullptr);
     }
-}
-
-template <int GW>
-static void an_launch_pair_bwd(bool has_y, bool has_z, unsigned grid, hipStream_t st, const float *gy, const float *gz, const float *y,
-                               const float *scale, const float *mask, float *gx, const AnGeom &G)
-{
-    const dim3 gd(grid), b(AN_TPB);
-    if (has_y && has_z) hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW, true, true>), gd, b, 0, st, gy, gz, y, scale, mask, gx, G);
-    else if (has_z) hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW, false, true>), gd, b, 0, st, gy, gz, y, scale, mask, gx, G);
-    else hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW, true, false>), gd, b, 0, st, gy, gz, y, scale, mask, gx, G);
 }
 
 
@@ -480,86 +422,62 @@ __global__ void __launch_bounds__(PF_TPB) k_pool_fold_table(const float *__restr
 // row class of a row: 0 top, 1 interior, 2 bottom
 __device__ __forceinline__ int pf_rc(int row, int H) { return row == 0 ? 0 : row == H - 1 ? 2 : 1; }
 
-template <int GW, bool FULL>
-__device__ __forceinline__ void pf_fwd_chunk(const float *__restrict__ z, float *__restrict__ y, int g0, int n, int H, int W, float sc, float sh,
-                                             const float *__restrict__ t)
-{
-    float zv[AN_U][GW];
+// in: z  out: y.  Row and column come from the group index: a group lies in one row on both routes
+struct PfFwd {
+    static constexpr bool IN[3] = {true, false, false}, OUT[2] = {true, false};
+    int H, W;
+    float sc, sh;
+    const float *t;                                             // the plane's table
+    template <int GW> __device__ __forceinline__ void group(int g, const float *const *in, float (*out)[GW]) const
+    {
+        const unsigned e0 = (unsigned)g * GW, row = e0 / (unsigned)W, col = e0 - row * (unsigned)W;
+        const float *tr = t + pf_rc((int)row, H) * 3;          // the plane's 36-byte table stays in the cache; a copy in registers
+        const float t0 = tr[0], t1 = tr[1], t2 = tr[2];        // picked by selects comes back from the compiler as an LDS array
 #pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) an_load<GW>(z + (size_t)g * GW, zv[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int g = g0 + u * AN_TPB;
-        if (FULL || g < n) {
-            const unsigned e0 = (unsigned)g * GW, row = e0 / (unsigned)W, col = e0 - row * (unsigned)W;
-            const float *tr = t + pf_rc((int)row, H) * 3;      // the plane's 36-byte table stays in the cache; a copy in registers
-            const float t0 = tr[0], t1 = tr[1], t2 = tr[2];    // picked by selects comes back from the compiler as an LDS array
-            float out[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                const int c = (int)col + e;
-                float s = zv[u][e] + (c == 0 ? t0 : c == W - 1 ? t2 : t1);
-                s = s * sc;
-                s = s + sh;
-                out[e] = s <= 0.0f ? 0.0f : s;
-            }
-            an_store<GW>(y + (size_t)g * GW, out);
+        for (int e = 0; e < GW; ++e) {
+            const int c = (int)col + e;
+            float s = in[0][e] + (c == 0 ? t0 : c == W - 1 ? t2 : t1);
+            s = s * sc;
+            s = s + sh;
+            out[0][e] = s <= 0.0f ? 0.0f : s;
         }
     }
-}
+};
 
 template <int GW>
 __global__ void __launch_bounds__(AN_TPB) k_pool_fold_fwd(const float *__restrict__ z, const float *__restrict__ T, const float *__restrict__ scale,
                                                           const float *__restrict__ shift, float *__restrict__ y, PfGeom G)
 {
-    const unsigned plane = blockIdx.x / (unsigned)G.a.cpp;
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.a.cpp), c = (int)(plane % (unsigned)G.a.C);
-    const size_t po = (size_t)plane * G.a.n * GW;
-    const float sc = scale[c], sh = shift[c];
-    const float *t = T + (size_t)plane * 9;
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.a.n - base >= AN_CHUNK) pf_fwd_chunk<GW, true>(z + po, y + po, g0, G.a.n, G.H, G.W, sc, sh, t);
-    else pf_fwd_chunk<GW, false>(z + po, y + po, g0, G.a.n, G.H, G.W, sc, sh, t);
+    const AnPlace P = an_place<GW>(G.a);
+    PfFwd op{G.H, G.W, scale[P.c], shift[P.c], T + (size_t)P.plane * 9};
+    an_walk<GW>(op, P, z, nullptr, nullptr, y, nullptr);
 }
 
-template <int GW, bool GZ, bool SUMS, bool FULL>
-__device__ __forceinline__ void pf_bwd_chunk(const float *__restrict__ g, const float *__restrict__ y, float *__restrict__ gz, int g0, int n, int H,
-                                             int W, float sc, double *acc)
-{
-    float gv[AN_U][GW], yv[AN_U][GW];
+// in: g, y  out: g_z.  SUMS: the lane's class sums of g_z, in element order, go to the kernel's acc (held in the op itself, the
+// 16-byte route's two SUMS kernels take 66 and 68 VGPRs instead of 56 and 62: 7 waves per SIMD)
+template <bool GZ, bool SUMS> struct PfBwd {
+    static constexpr bool IN[3] = {true, true, false}, OUT[2] = {GZ, false};
+    int H, W;
+    float sc;
+    double *acc;
+    template <int GW> __device__ __forceinline__ void group(int g, const float *const *in, float (*out)[GW]) const
+    {
+        const unsigned e0 = (unsigned)g * GW, row = e0 / (unsigned)W, col = e0 - row * (unsigned)W;
+        const int rc = pf_rc((int)row, H);
 #pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int q = g0 + u * AN_TPB;
-        if (FULL || q < n) {
-            an_load<GW>(g + (size_t)q * GW, gv[u]);
-            an_load<GW>(y + (size_t)q * GW, yv[u]);
-        }
-    }
+        for (int e = 0; e < GW; ++e) {
+            const float gv = in[0][e];                       // read in front of the gate: as the gate's own operand the first group's
+            const float gp = in[1][e] <= 0.0f ? 0.0f : gv;     // load of g is moved under it and issued when y has arrived
+            out[0][e] = gp * sc;
+            if constexpr (SUMS) {
+                const int c = (int)col + e, cls = rc * 3 + (c == 0 ? 0 : c == W - 1 ? 2 : 1);
+                const double d = (double)out[0][e];
 #pragma unroll
-    for (int u = 0; u < AN_U; ++u) {
-        const int q = g0 + u * AN_TPB;
-        if (FULL || q < n) {
-            const unsigned e0 = (unsigned)q * GW, row = e0 / (unsigned)W, col = e0 - row * (unsigned)W;
-            const int rc = pf_rc((int)row, H);
-            float ox[GW];
-#pragma unroll
-            for (int e = 0; e < GW; ++e) {
-                const float gp = yv[u][e] <= 0.0f ? 0.0f : gv[u][e];
-                ox[e] = gp * sc;
-                if constexpr (SUMS) {
-                    const int c = (int)col + e, cls = rc * 3 + (c == 0 ? 0 : c == W - 1 ? 2 : 1);
-                    const double d = (double)ox[e];
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) acc[k] += cls == k ? d : 0.0;
-                }
+                for (int k = 0; k < 9; ++k) acc[k] += cls == k ? d : 0.0;
             }
-            if constexpr (GZ) an_store<GW>(gz + (size_t)q * GW, ox);
         }
     }
-}
+};
 
 template <int GW, bool GZ, bool SUMS>
 __global__ void __launch_bounds__(AN_TPB) k_pool_fold_bwd(const float *__restrict__ g, const float *__restrict__ y, const float *__restrict__ scale,
@@ -567,15 +485,10 @@ __global__ void __launch_bounds__(AN_TPB) k_pool_fold_bwd(const float *__restric
 {
     static_assert(AN_TPB == PF_TPB, "pf_tree is sized for the plane walk's workgroup");
     __shared__ double red[SUMS ? 9 : 1][PF_TPB];
-    const unsigned plane = blockIdx.x / (unsigned)G.a.cpp;
-    const int chunk = (int)(blockIdx.x - plane * (unsigned)G.a.cpp), c = (int)(plane % (unsigned)G.a.C);
-    const size_t po = (size_t)plane * G.a.n * GW;
-    const float sc = scale[c];
-    float *zp = GZ ? gz + po : nullptr;
+    const AnPlace P = an_place<GW>(G.a);
     double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int base = chunk * AN_CHUNK, g0 = base + (int)threadIdx.x;
-    if (G.a.n - base >= AN_CHUNK) pf_bwd_chunk<GW, GZ, SUMS, true>(g + po, y + po, zp, g0, G.a.n, G.H, G.W, sc, acc);
-    else pf_bwd_chunk<GW, GZ, SUMS, false>(g + po, y + po, zp, g0, G.a.n, G.H, G.W, sc, acc);
+    PfBwd<GZ, SUMS> op{G.H, G.W, scale[P.c], acc};
+    an_walk<GW>(op, P, g, y, nullptr, gz, nullptr);
     if constexpr (SUMS) {
         pf_tree(red, acc, (int)threadIdx.x);
         if (threadIdx.x < 9) slab[(size_t)blockIdx.x * 9 + threadIdx.x] = red[threadIdx.x][0];
@@ -613,16 +526,6 @@ static bool pf_vec(int64_t W, const void *p0, const void *p1, const void *p2)
 // rows of the slab per plane: sized for the one-element route, which cuts a plane into the most chunks
 static int64_t pf_slab_rows(int64_t H, int64_t W) { return cdiv(H * W, AN_CHUNK); }
 
-template <int GW>
-static void pf_launch_bwd(bool want_z, bool sums, unsigned grid, hipStream_t st, const float *g, const float *y, const float *scale, float *gz,
-                          double *slab, const PfGeom &G)
-{
-    const dim3 gd(grid), b(AN_TPB);
-    if (want_z && sums) hipLaunchKernelGGL((k_pool_fold_bwd<GW, true, true>), gd, b, 0, st, g, y, scale, gz, slab, G);
-    else if (want_z) hipLaunchKernelGGL((k_pool_fold_bwd<GW, true, false>), gd, b, 0, st, g, y, scale, gz, slab, G);
-    else hipLaunchKernelGGL((k_pool_fold_bwd<GW, false, true>), gd, b, 0, st, g, y, scale, gz, slab, G);
-}
-
 }  // namespace halo
 
 using namespace halo;
@@ -634,14 +537,12 @@ extern "C" int halo_affine_relu_fwd(const float *x, const float *scale, const fl
     if (!x || !scale || !shift || !y) return fail(HALO_E_ARG, "%s: null argument", who);
     if ((r_scale == nullptr) != (r_shift == nullptr)) return fail(HALO_E_ARG, "%s: r_scale and r_shift are given together or not at all", who);
     if (r_scale && !r) return fail(HALO_E_ARG, "%s: r_scale without a residual operand", who);
-    const bool vec = an_vec(HW, x, y, r, nullptr);
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    const int res = !r ? AN_NONE : r_scale ? AN_AFFINE : AN_PLAIN;
-    if (vec) an_launch_fwd<4>(res, grid, (hipStream_t)stream, x, scale, shift, r, r_scale, r_shift, y, G);
-    else an_launch_fwd<1>(res, grid, (hipStream_t)stream, x, scale, shift, r, r_scale, r_shift, y, G);
-    return check_launch(who);
+    return an_run(who, B, C, HW, an_vec(HW, x, y, r, nullptr), [&](auto GW, const AnGeom &G, dim3 grid) {
+        an_flags([&](auto R, auto RAFF) {
+            constexpr int RES = !R() ? AN_NONE : RAFF() ? AN_AFFINE : AN_PLAIN;
+            hipLaunchKernelGGL((k_affine_relu_fwd<GW(), RES>), grid, dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, r, r_scale, r_shift, y, G);
+        }, r != nullptr, r_scale != nullptr);
+    });
 }
 
 // both entries of the block tail's backward: g_b is the second gradient of halo_fork_affine_relu_bwd, null for the single one
@@ -651,19 +552,13 @@ static int an_bwd_entry(const char *who, const float *g, const float *g_b, const
     if (!g_x && !g_r) return fail(HALO_E_ARG, "%s: neither g_x nor g_r is asked for", who);
     if (g_x && !scale) return fail(HALO_E_ARG, "%s: g_x needs scale", who);
     const bool vec = an_vec(HW, g, y, g_x, g_r) && (uintptr_t)g_b % 16 == 0;
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    const bool raff = g_r && r_scale, wx = g_x != nullptr, wr = g_r != nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (g_b) {
-        if (vec) an_launch_bwd<4, true>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
-        else an_launch_bwd<1, true>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
-    } else {
-        if (vec) an_launch_bwd<4, false>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
-        else an_launch_bwd<1, false>(wx, wr, raff, grid, st, g, g_b, y, scale, r_scale, g_x, g_r, G);
-    }
-    return check_launch(who);
+    return an_run(who, B, C, HW, vec, [&](auto GW, const AnGeom &G, dim3 grid) {
+        an_flags([&](auto GX, auto GR, auto RAFF, auto FORK) {
+            if constexpr ((GX() || GR()) && (GR() || !RAFF()))       // r_scale counts only where g_r is asked for
+                hipLaunchKernelGGL((k_affine_relu_bwd<GW(), GX(), GR(), RAFF(), FORK()>), grid, dim3(AN_TPB), 0, (hipStream_t)stream, g, g_b, y,
+                                   scale, r_scale, g_x, g_r, G);
+        }, g_x != nullptr, g_r != nullptr, g_r && r_scale, g_b != nullptr);
+    });
 }
 
 extern "C" int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *r_scale, float *g_x, float *g_r,
@@ -687,13 +582,9 @@ extern "C" int halo_masked_affine_relu_fwd(const float *x, const float *scale, c
 {
     const char *who = "halo_masked_affine_relu_fwd";
     if (!x || !scale || !shift || !mask || !y) return fail(HALO_E_ARG, "%s: null argument", who);
-    const bool vec = an_vec(HW, x, y, nullptr, nullptr);
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    if (vec) hipLaunchKernelGGL((k_affine_relu_mask_fwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, G);
-    else hipLaunchKernelGGL((k_affine_relu_mask_fwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, G);
-    return check_launch(who);
+    return an_run(who, B, C, HW, an_vec(HW, x, y, nullptr, nullptr), [&](auto GW, const AnGeom &G, dim3 grid) {
+        hipLaunchKernelGGL((k_affine_relu_mask_fwd<GW()>), grid, dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, G);
+    });
 }
 
 extern "C" int halo_masked_affine_relu_bwd(const float *g, const float *y, const float *scale, const float *mask, float *g_x, int64_t B,
@@ -701,13 +592,9 @@ extern "C" int halo_masked_affine_relu_bwd(const float *g, const float *y, const
 {
     const char *who = "halo_masked_affine_relu_bwd";
     if (!g || !y || !scale || !mask || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
-    const bool vec = an_vec(HW, g, y, g_x, nullptr);
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    if (vec) hipLaunchKernelGGL((k_affine_relu_mask_bwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
-    else hipLaunchKernelGGL((k_affine_relu_mask_bwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
-    return check_launch(who);
+    return an_run(who, B, C, HW, an_vec(HW, g, y, g_x, nullptr), [&](auto GW, const AnGeom &G, dim3 grid) {
+        hipLaunchKernelGGL((k_affine_relu_mask_bwd<GW()>), grid, dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, mask, g_x, G);
+    });
 }
 
 extern "C" int halo_dropout_pair_fwd(const float *x, const float *scale, const float *shift, const float *mask, float *y, float *z, int64_t B,
@@ -715,13 +602,9 @@ extern "C" int halo_dropout_pair_fwd(const float *x, const float *scale, const f
 {
     const char *who = "halo_dropout_pair_fwd";
     if (!x || !scale || !shift || !mask || !y || !z) return fail(HALO_E_ARG, "%s: null argument", who);
-    const bool vec = an_vec(HW, x, y, z, nullptr);
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    if (vec) hipLaunchKernelGGL((k_affine_relu_pair_fwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, z, G);
-    else hipLaunchKernelGGL((k_affine_relu_pair_fwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, z, G);
-    return check_launch(who);
+    return an_run(who, B, C, HW, an_vec(HW, x, y, z, nullptr), [&](auto GW, const AnGeom &G, dim3 grid) {
+        hipLaunchKernelGGL((k_affine_relu_pair_fwd<GW()>), grid, dim3(AN_TPB), 0, (hipStream_t)stream, x, scale, shift, mask, y, z, G);
+    });
 }
 
 extern "C" int halo_dropout_pair_bwd(const float *g_y, const float *g_z, const float *y, const float *scale, const float *mask, float *g_x,
@@ -730,13 +613,13 @@ extern "C" int halo_dropout_pair_bwd(const float *g_y, const float *g_z, const f
     const char *who = "halo_dropout_pair_bwd";
     if (!y || !scale || !mask || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
     if (!g_y && !g_z) return fail(HALO_E_ARG, "%s: null argument: neither g_y nor g_z is given", who);
-    const bool vec = an_vec(HW, g_y, g_z, y, g_x);
-    AnGeom G;
-    unsigned grid;
-    if (int rc = an_plan(who, B, C, HW, vec, G, grid)) return rc;
-    if (vec) an_launch_pair_bwd<4>(g_y != nullptr, g_z != nullptr, grid, (hipStream_t)stream, g_y, g_z, y, scale, mask, g_x, G);
-    else an_launch_pair_bwd<1>(g_y != nullptr, g_z != nullptr, grid, (hipStream_t)stream, g_y, g_z, y, scale, mask, g_x, G);
-    return check_launch(who);
+    return an_run(who, B, C, HW, an_vec(HW, g_y, g_z, y, g_x), [&](auto GW, const AnGeom &G, dim3 grid) {
+        an_flags([&](auto GY, auto GZ) {
+            if constexpr (GY() || GZ())
+                hipLaunchKernelGGL((k_affine_relu_pair_bwd<GW(), GY(), GZ()>), grid, dim3(AN_TPB), 0, (hipStream_t)stream, g_y, g_z, y, scale, mask,
+                                   g_x, G);
+        }, g_y != nullptr, g_z != nullptr);
+    });
 }
 
 extern "C" size_t halo_pool_fold_workspace_bytes(int64_t B, int64_t Co, int64_t H, int64_t W)
@@ -773,8 +656,9 @@ extern "C" int halo_pool_fold_affine_relu_fwd(const float *z, const float *T, co
     PfGeom G;
     unsigned grid;
     if (int rc = pf_plan(who, B, Co, H, W, vec, G, grid)) return rc;
-    if (vec) hipLaunchKernelGGL((k_pool_fold_fwd<4>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, z, T, scale, shift, y, G);
-    else hipLaunchKernelGGL((k_pool_fold_fwd<1>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, z, T, scale, shift, y, G);
+    an_route(vec, [&](auto GW) {
+        hipLaunchKernelGGL((k_pool_fold_fwd<GW()>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, z, T, scale, shift, y, G);
+    });
     return check_launch(who);
 }
 
@@ -795,8 +679,12 @@ extern "C" int halo_pool_fold_affine_relu_bwd(const float *g, const float *y, co
         if (!slab) return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, halo_pool_fold_workspace_bytes gives %zu", who, workspace_bytes,
                                halo_pool_fold_workspace_bytes(B, Co, H, W));
     }
-    if (vec) pf_launch_bwd<4>(g_z != nullptr, g_T != nullptr, grid, (hipStream_t)stream, g, y, scale, g_z, slab, G);
-    else pf_launch_bwd<1>(g_z != nullptr, g_T != nullptr, grid, (hipStream_t)stream, g, y, scale, g_z, slab, G);
+    an_route(vec, [&](auto GW) {
+        an_flags([&](auto GZ, auto SUMS) {
+            if constexpr (GZ() || SUMS())
+                hipLaunchKernelGGL((k_pool_fold_bwd<GW(), GZ(), SUMS()>), dim3(grid), dim3(AN_TPB), 0, (hipStream_t)stream, g, y, scale, g_z, slab, G);
+        }, g_z != nullptr, g_T != nullptr);
+    });
     if (g_T) {
         const int64_t entries = B * Co * 9;
         hipLaunchKernelGGL(k_pool_fold_finish, dim3((unsigned)cdiv(entries, PF_TPB)), dim3(PF_TPB), 0, (hipStream_t)stream, slab, g_T, entries,

@@ -83,15 +83,30 @@ def _norm_reason(bn, C, device, what):
     return None
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(getattr(t, "requires_grad", False) for t in tensors)
+
+
+def _speed_reason(reason, least, x, *others):
+    """a *_fallback_reason behind its envelope's `reason`: the speed rule's sentence for a served x of fewer than `least` elements
+    when it, or one of `others`, will be asked for a gradient"""
+    if reason is None and _wants_grad(x, *others) and x.numel() < least:
+        return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (x.numel(), least)
+    return reason
+
+
+def _call(key, name, device, tensors, *dims):
+    """one launch, counted under launches[key]: the library's entry `name`, looked up when it is called, over the tensors'
+    pointers (None: a null pointer), the dimensions and the device's current stream"""
+    launches[key] += 1
+    _lib.check(getattr(_lib.lib(), name)(*[_lib.ptr(t) for t in tensors], *dims, _lib.stream_ptr(device)), name)
+
+
 def fallback_reason(x, bn, residual=None, residual_bn=None):
     """why norm_relu(x, bn, residual, residual_bn) runs the torch statements (None: the fused path serves it).  Reads no device
     memory."""
-    reason = _envelope_reason(x, bn, residual, residual_bn)
-    if reason is None and torch.is_grad_enabled() and (getattr(x, "requires_grad", False) or getattr(residual, "requires_grad", False)):
-        least = AUTOGRAD_MIN_ELEMENTS["affine" if residual_bn is not None else "plain"]
-        if x.numel() < least:
-            return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (x.numel(), least)
-    return reason
+    return _speed_reason(_envelope_reason(x, bn, residual, residual_bn), AUTOGRAD_MIN_ELEMENTS["affine" if residual_bn is not None else "plain"],
+                         x, residual)
 
 
 def _envelope_reason(x, bn, residual, residual_bn):
@@ -153,33 +168,48 @@ def forget(bn=None):
         _cache.pop(bn, None)
 
 
+def _tail_forward(ctx, x, scale, shift, r, r_scale, r_shift):
+    """the forward of both block-tail nodes"""
+    B, C, H, W = x.shape
+    y = torch.empty_like(x)
+    _call("fwd", "halo_affine_relu_fwd", x.device, (x, scale, shift, r, r_scale, r_shift, y), B, C, H * W)
+    ctx.save_for_backward(y, scale, r_scale)
+    return y
+
+
+def _tail_backward(ctx, *grads):
+    """the backward of both: (g_x, g_r) from the gradients that arrived at y, one pass for one of them and for two"""
+    y, scale, r_scale = ctx.saved_tensors
+    B, C, H, W = y.shape
+    want_x, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+    grads = [g for g in grads if g is not None]
+    if not (want_x or want_r) or not grads:
+        return None, None
+    grads = [g.to(device=y.device, dtype=torch.float32).contiguous() for g in grads]
+    gx = torch.empty_like(y) if want_x else None
+    gr = torch.empty_like(y) if want_r else None
+    if len(grads) == 2:
+        _call("fork_bwd", "halo_fork_affine_relu_bwd", y.device, (grads[0], grads[1], y, scale, r_scale, gx, gr), B, C, H * W)
+    else:
+        _call("bwd", "halo_affine_relu_bwd", y.device, (grads[0], y, scale, r_scale, gx, gr), B, C, H * W)
+    return gx, gr
+
+
 class _NormReluFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, scale, shift, r, r_scale, r_shift):
-        B, C, H, W = x.shape
-        y = torch.empty_like(x)
-        launches["fwd"] += 1
-        _lib.check(_lib.lib().halo_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(r), _lib.ptr(r_scale),
-                                                   _lib.ptr(r_shift), _lib.ptr(y), B, C, H * W, _lib.stream_ptr(x.device)),
-                   "halo_affine_relu_fwd")
-        ctx.save_for_backward(y, scale, r_scale)
-        return y
+    forward = staticmethod(_tail_forward)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        y, scale, r_scale = ctx.saved_tensors
-        B, C, H, W = y.shape
-        want_x, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
-        gx = gr = None
-        if want_x or want_r:
-            g = g.to(device=y.device, dtype=torch.float32).contiguous()
-            gx = torch.empty_like(y) if want_x else None
-            gr = torch.empty_like(y) if want_r else None
-            launches["bwd"] += 1
-            _lib.check(_lib.lib().halo_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(r_scale), _lib.ptr(gx),
-                                                       _lib.ptr(gr), B, C, H * W, _lib.stream_ptr(y.device)), "halo_affine_relu_bwd")
+        gx, gr = _tail_backward(ctx, g)
         return gx, None, None, gr, None, None
+
+
+def _tail_operands(x, bn, residual, residual_bn):
+    """the arguments of both block-tail nodes, for arguments that the envelope has accepted"""
+    scale, shift = cached_scale_shift(bn)
+    r_scale, r_shift = cached_scale_shift(residual_bn) if residual_bn is not None else (None, None)
+    return x, scale, shift, residual, r_scale, r_shift
 
 
 def norm_relu(x, bn, residual=None, residual_bn=None):
@@ -193,11 +223,7 @@ def norm_relu(x, bn, residual=None, residual_bn=None):
 
 def fused_norm_relu(x, bn, residual=None, residual_bn=None):
     """norm_relu for arguments that fallback_reason has accepted"""
-    scale, shift = cached_scale_shift(bn)
-    r_scale = r_shift = None
-    if residual_bn is not None:
-        r_scale, r_shift = cached_scale_shift(residual_bn)
-    return _NormReluFn.apply(x, scale, shift, residual, r_scale, r_shift)
+    return _NormReluFn.apply(*_tail_operands(x, bn, residual, residual_bn))
 
 
 # ---------------------------------------------------------------- a block tail whose output is read twice
@@ -223,7 +249,7 @@ def fork_fallback_reason(x, bn, residual=None, residual_bn=None):
     reason = _envelope_reason(x, bn, residual, residual_bn)
     if reason is not None:
         return reason
-    if not (torch.is_grad_enabled() and (getattr(x, "requires_grad", False) or getattr(residual, "requires_grad", False))):
+    if not _wants_grad(x, residual):
         return "no gradient will be asked for"
     if x.numel() < FORK_AUTOGRAD_MIN_ELEMENTS:
         return "%d elements are fewer than the %d from which the two-gradient backward was measured faster" % (
@@ -233,38 +259,15 @@ def fork_fallback_reason(x, bn, residual=None, residual_bn=None):
 
 class _NormReluForkFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, scale, shift, r, r_scale, r_shift):
-        B, C, H, W = x.shape
-        y = torch.empty_like(x)
-        launches["fwd"] += 1
-        _lib.check(_lib.lib().halo_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(r), _lib.ptr(r_scale),
-                                                   _lib.ptr(r_shift), _lib.ptr(y), B, C, H * W, _lib.stream_ptr(x.device)),
-                   "halo_affine_relu_fwd")
-        ctx.save_for_backward(y, scale, r_scale)
+    def forward(ctx, *operands):
+        y = _tail_forward(ctx, *operands)
         ctx.set_materialize_grads(False)                   # an output nobody used arrives as None and is not read
         return y, y.view_as(y)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_a, g_b):
-        y, scale, r_scale = ctx.saved_tensors
-        B, C, H, W = y.shape
-        want_x, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
-        gx = gr = None
-        if (want_x or want_r) and (g_a is not None or g_b is not None):
-            g_a, g_b = (None if g is None else g.to(device=y.device, dtype=torch.float32).contiguous() for g in (g_a, g_b))
-            gx = torch.empty_like(y) if want_x else None
-            gr = torch.empty_like(y) if want_r else None
-            if g_a is not None and g_b is not None:
-                launches["fork_bwd"] += 1
-                _lib.check(_lib.lib().halo_fork_affine_relu_bwd(_lib.ptr(g_a), _lib.ptr(g_b), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(r_scale),
-                                                                _lib.ptr(gx), _lib.ptr(gr), B, C, H * W, _lib.stream_ptr(y.device)),
-                           "halo_fork_affine_relu_bwd")
-            else:
-                g = g_a if g_a is not None else g_b
-                launches["bwd"] += 1
-                _lib.check(_lib.lib().halo_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(r_scale), _lib.ptr(gx),
-                                                           _lib.ptr(gr), B, C, H * W, _lib.stream_ptr(y.device)), "halo_affine_relu_bwd")
+        gx, gr = _tail_backward(ctx, g_a, g_b)
         return gx, None, None, gr, None, None
 
 
@@ -279,11 +282,7 @@ def norm_relu_fork(x, bn, residual=None, residual_bn=None):
     if fork_fallback_reason(x, bn, residual, residual_bn) is not None:
         t = norm_relu(x, bn, residual, residual_bn)
         return t, t
-    scale, shift = cached_scale_shift(bn)
-    r_scale = r_shift = None
-    if residual_bn is not None:
-        r_scale, r_shift = cached_scale_shift(residual_bn)
-    return _NormReluForkFn.apply(x, scale, shift, residual, r_scale, r_shift)
+    return _NormReluForkFn.apply(*_tail_operands(x, bn, residual, residual_bn))
 
 
 # ---------------------------------------------------------------- norm + ReLU + Dropout2d
@@ -301,9 +300,8 @@ def dropout_statement(x, bn, drop):
     return drop(F.relu(bn(x), inplace=True))
 
 
-def dropout_fallback_reason(x, bn, drop):
-    """why norm_relu_dropout2d(x, bn, drop) runs the torch statements (None: a fused pass serves it -- the masked one when drop is
-    in training mode with 0 < p < 1, norm_relu's otherwise).  Reads no device memory."""
+def _drop_reason(x, bn, drop, least):
+    """dropout_fallback_reason and pair_fallback_reason, which differ in the speed rule's threshold alone"""
     if not isinstance(drop, nn.Dropout2d):
         return "drop is not an nn.Dropout2d"
     if drop.inplace:
@@ -312,12 +310,19 @@ def dropout_fallback_reason(x, bn, drop):
         return fallback_reason(x, bn)                      # nothing is drawn: relu(bn(x)) alone
     if drop.p >= 1:
         return "p = 1 drops every plane"
-    reason = _envelope_reason(x, bn, None, None)
-    if reason is None and torch.is_grad_enabled() and getattr(x, "requires_grad", False):
-        least = AUTOGRAD_MIN_ELEMENTS.get("masked", 0)
-        if x.numel() < least:
-            return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (x.numel(), least)
-    return reason
+    return _speed_reason(_envelope_reason(x, bn, None, None), least, x)
+
+
+def _noise(x, drop):
+    """nn.Dropout2d's multiplier per (image, channel), drawn with ATen's statements (_dropout_impl, feature dropout)"""
+    B, C = x.shape[:2]
+    return x.new_empty((B, C, 1, 1)).bernoulli_(1 - drop.p).div_(1 - drop.p)
+
+
+def dropout_fallback_reason(x, bn, drop):
+    """why norm_relu_dropout2d(x, bn, drop) runs the torch statements (None: a fused pass serves it -- the masked one when drop is
+    in training mode with 0 < p < 1, norm_relu's otherwise).  Reads no device memory."""
+    return _drop_reason(x, bn, drop, AUTOGRAD_MIN_ELEMENTS.get("masked", 0))
 
 
 class _NormReluDropFn(torch.autograd.Function):
@@ -325,9 +330,7 @@ class _NormReluDropFn(torch.autograd.Function):
     def forward(ctx, x, scale, shift, noise):
         B, C, H, W = x.shape
         y = torch.empty_like(x)
-        launches["masked_fwd"] += 1
-        _lib.check(_lib.lib().halo_masked_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(noise), _lib.ptr(y),
-                                                          B, C, H * W, _lib.stream_ptr(x.device)), "halo_masked_affine_relu_fwd")
+        _call("masked_fwd", "halo_masked_affine_relu_fwd", x.device, (x, scale, shift, noise, y), B, C, H * W)
         ctx.save_for_backward(y, scale, noise)
         return y
 
@@ -340,9 +343,7 @@ class _NormReluDropFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             g = g.to(device=y.device, dtype=torch.float32).contiguous()
             gx = torch.empty_like(y)
-            launches["masked_bwd"] += 1
-            _lib.check(_lib.lib().halo_masked_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(noise), _lib.ptr(gx),
-                                                              B, C, H * W, _lib.stream_ptr(y.device)), "halo_masked_affine_relu_bwd")
+            _call("masked_bwd", "halo_masked_affine_relu_bwd", y.device, (g, y, scale, noise, gx), B, C, H * W)
         return gx, None, None, None
 
 
@@ -357,10 +358,7 @@ def norm_relu_dropout2d(x, bn, drop):
         return dropout_statement(x, bn, drop)
     if not drop.training or drop.p == 0:
         return fused_norm_relu(x, bn)
-    B, C = x.shape[:2]
-    noise = x.new_empty((B, C, 1, 1)).bernoulli_(1 - drop.p).div_(1 - drop.p)          # ATen's _dropout_impl, feature dropout
-    scale, shift = cached_scale_shift(bn)
-    return _NormReluDropFn.apply(x, scale, shift, noise)
+    return _NormReluDropFn.apply(x, *cached_scale_shift(bn), _noise(x, drop))
 
 
 # ---------------------------------------------------------------- norm + ReLU + Dropout2d, both tensors kept
@@ -389,19 +387,7 @@ def pair_fallback_reason(x, bn, drop):
     """why norm_relu_dropout2d_pair(x, bn, drop) runs the torch statements (None: a fused pass serves it -- the two-output one when
     drop is in training mode with 0 < p < 1, norm_relu's otherwise).  The envelope is norm_relu_dropout2d's.  Reads no device
     memory."""
-    if not isinstance(drop, nn.Dropout2d):
-        return "drop is not an nn.Dropout2d"
-    if drop.inplace:
-        return "the dropout is in place"
-    if not drop.training or drop.p == 0:
-        return fallback_reason(x, bn)                      # nothing is drawn: relu(bn(x)) alone
-    if drop.p >= 1:
-        return "p = 1 drops every plane"
-    reason = _envelope_reason(x, bn, None, None)
-    if reason is None and torch.is_grad_enabled() and getattr(x, "requires_grad", False) and x.numel() < PAIR_AUTOGRAD_MIN_ELEMENTS:
-        return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (
-            x.numel(), PAIR_AUTOGRAD_MIN_ELEMENTS)
-    return reason
+    return _drop_reason(x, bn, drop, PAIR_AUTOGRAD_MIN_ELEMENTS)
 
 
 class _NormReluDropPairFn(torch.autograd.Function):
@@ -409,9 +395,7 @@ class _NormReluDropPairFn(torch.autograd.Function):
     def forward(ctx, x, scale, shift, noise):
         B, C, H, W = x.shape
         y, z = torch.empty_like(x), torch.empty_like(x)
-        launches["pair_fwd"] += 1
-        _lib.check(_lib.lib().halo_dropout_pair_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(noise), _lib.ptr(y), _lib.ptr(z),
-                                                    B, C, H * W, _lib.stream_ptr(x.device)), "halo_dropout_pair_fwd")
+        _call("pair_fwd", "halo_dropout_pair_fwd", x.device, (x, scale, shift, noise, y, z), B, C, H * W)
         ctx.save_for_backward(y, scale, noise)
         ctx.set_materialize_grads(False)                   # an output nobody used arrives as None and is not read
         return y, z
@@ -425,9 +409,7 @@ class _NormReluDropPairFn(torch.autograd.Function):
         if ctx.needs_input_grad[0] and (g_y is not None or g_z is not None):
             g_y, g_z = (None if g is None else g.to(device=y.device, dtype=torch.float32).contiguous() for g in (g_y, g_z))
             gx = torch.empty_like(y)
-            launches["pair_bwd"] += 1
-            _lib.check(_lib.lib().halo_dropout_pair_bwd(_lib.ptr(g_y), _lib.ptr(g_z), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(noise),
-                                                        _lib.ptr(gx), B, C, H * W, _lib.stream_ptr(y.device)), "halo_dropout_pair_bwd")
+            _call("pair_bwd", "halo_dropout_pair_bwd", y.device, (g_y, g_z, y, scale, noise, gx), B, C, H * W)
         return gx, None, None, None
 
 
@@ -444,10 +426,7 @@ def norm_relu_dropout2d_pair(x, bn, drop):
     if not drop.training or drop.p == 0:
         y = fused_norm_relu(x, bn)
         return y, y
-    B, C = x.shape[:2]
-    noise = x.new_empty((B, C, 1, 1)).bernoulli_(1 - drop.p).div_(1 - drop.p)          # ATen's _dropout_impl, feature dropout
-    scale, shift = cached_scale_shift(bn)
-    return _NormReluDropPairFn.apply(x, scale, shift, noise)
+    return _NormReluDropPairFn.apply(x, *cached_scale_shift(bn), _noise(x, drop))
 
 
 # ---------------------------------------------------------------- norm + ReLU + MaxPool2d(3, 2, 1): the stem
@@ -499,13 +478,7 @@ def _pool_reason(pool):
 
 def pool_fallback_reason(x, bn, pool):
     """why norm_relu_maxpool(x, bn, pool) runs the torch statements (None: the fused pass serves it).  Reads no device memory."""
-    reason = _pool_reason(pool)
-    if reason is None:
-        reason = _envelope_reason(x, bn, None, None)
-    if reason is None and torch.is_grad_enabled() and getattr(x, "requires_grad", False) and x.numel() < POOL_AUTOGRAD_MIN_ELEMENTS:
-        return "under autograd %d elements are fewer than the %d from which the fused pair was measured faster" % (
-            x.numel(), POOL_AUTOGRAD_MIN_ELEMENTS)
-    return reason
+    return _speed_reason(_pool_reason(pool) or _envelope_reason(x, bn, None, None), POOL_AUTOGRAD_MIN_ELEMENTS, x)
 
 
 class _NormReluPoolFn(torch.autograd.Function):
@@ -515,10 +488,8 @@ class _NormReluPoolFn(torch.autograd.Function):
         shape = (B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
         out = x.new_empty(shape)
         tap = torch.empty(shape, dtype=torch.uint8, device=x.device) if keep else None      # no backward will come: no codes
-        launches["pool_fwd"] += 1
         launches["pool_taps"] += keep
-        _lib.check(_lib.lib().halo_maxpool_affine_relu_fwd(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(out), _lib.ptr(tap),
-                                                           B, C, H, W, _lib.stream_ptr(x.device)), "halo_maxpool_affine_relu_fwd")
+        _call("pool_fwd", "halo_maxpool_affine_relu_fwd", x.device, (x, scale, shift, out, tap), B, C, H, W)
         if keep:
             ctx.save_for_backward(tap, scale)
         ctx.x_shape = (B, C, H, W)
@@ -533,9 +504,7 @@ class _NormReluPoolFn(torch.autograd.Function):
             B, C, H, W = ctx.x_shape
             g = g.to(device=tap.device, dtype=torch.float32).contiguous()
             gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=tap.device)
-            launches["pool_bwd"] += 1
-            _lib.check(_lib.lib().halo_maxpool_affine_relu_bwd(_lib.ptr(g), _lib.ptr(tap), _lib.ptr(scale), _lib.ptr(gx), B, C, H, W,
-                                                               _lib.stream_ptr(tap.device)), "halo_maxpool_affine_relu_bwd")
+            _call("pool_bwd", "halo_maxpool_affine_relu_bwd", tap.device, (g, tap, scale, gx), B, C, H, W)
         return gx, None, None, None
 
 

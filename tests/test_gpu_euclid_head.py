@@ -15,9 +15,10 @@ from euclid_head_standin import Block, EuclidHead, frozen
 pytestmark = pytest.mark.gpu
 
 # the operator's cases: (B, C, H, W).  The first three have planes that are no multiple of four elements (one element per lane:
-# two chunks, one ragged chunk, five chunks); the last two take the 16-byte route (one ragged chunk; two chunks, the second ragged)
+# two chunks, one ragged chunk, five chunks); the last three take the 16-byte route (one ragged chunk; two chunks, the second ragged;
+# the same with B = 2, C = 3, so that plane, channel and mask index all differ -- named to sort last: seeds are places in sorted order)
 CASES = {"head": (2, 16, 33, 49), "tiny": (1, 3, 1, 5), "one_plane": (1, 1, 1, 4099), "vector_ragged": (2, 3, 4, 8),
-         "vector_two_blocks": (1, 2, 33, 128)}
+         "vector_two_blocks": (1, 2, 33, 128), "work_split_images": (2, 3, 33, 128)}
 NATIVE = ("halo_affine_relu_fwd", "halo_dwconv3x3_affine_relu_fwd", "halo_upcat_dwconv3x3_affine_relu_fwd", "halo_pool_fold_affine_relu_fwd",
           "halo_dropout_pair_fwd", "halo_dropout_pair_bwd", "halo_masked_affine_relu_fwd", "halo_bilinear_upsample", "halo_hfr_fwd_apply")
 

@@ -18,6 +18,8 @@ SHAPES = {
     "several_blocks_large": (1, 3, 160, 320),    # HW = 51200: twelve full chunks and a partial one
     "odd_multiple_of_four": (1, 2, 37, 52),      # HW = 1924 = 4 * 481: no multiple of a wave, a block or a chunk
     "unaligned_view": (1, 2, 8, 12),             # storage offset of one element: operands off 16 bytes
+    "scalar_whole_chunk": (2, 3, 13, 79),        # HW = 1027: one element per lane, a whole chunk of 1024 and three elements more
+    "unaligned_chunks": (1, 2, 33, 128),         # the same offset over HW = 4224: four whole chunks of single elements, a ragged fifth
 }
 VARIANTS = ("none", "plain", "affine")
 
@@ -68,7 +70,7 @@ def cases():
     for si, (name, shape) in enumerate(SHAPES.items()):
         for vi, variant in enumerate(VARIANTS):
             gen = torch.Generator().manual_seed(100 * si + vi)
-            un = name == "unaligned_view"
+            un = name.startswith("unaligned")
             bn = _norm(shape[1], 7 + si)
             rbn = _norm(shape[1], 70 + si) if variant == "affine" else None
             x = _tensor(shape, gen, un, True)

@@ -21,6 +21,10 @@ CASES = {
     "one_element": (2, 5, 3, 7, 0),                 # HW = 21: the one-element route
     "two_blocks": (1, 2, 33, 128, 0),               # 4224 elements: two workgroups of the 16-byte route, the second ragged
     "five_blocks_offset": (1, 2, 33, 128, 1),       # behind a 4-byte storage offset: five workgroups of the one-element route
+    # the same two with B = 2, C = 3, so that plane, channel and mask index all differ in whole and ragged chunks alike; named to
+    # sort behind the others, whose seeds are their places in the sorted names
+    "work_split_images": (2, 3, 33, 128, 0),
+    "work_split_images_offset": (2, 3, 33, 128, 1),
 }
 MASKS = ("kept", "dropped", "mixed")
 KEEP = float(torch.tensor(1.0).div(1 - 0.1))        # fl32(1 / (1 - p)) as noise.div_(1 - p) leaves it

@@ -49,6 +49,10 @@ CASES = {
     "two_blocks": (1, 2, 33, 128, 5, 0),            # 4224 elements: two workgroups of the 16-byte route, the second ragged
     "five_blocks_offset": (1, 2, 33, 128, 5, 3),    # five workgroups of the one-element route, the last ragged
     "wide_pool": (2, 2, 3, 4, 300, 0),              # Cg above and no multiple of the fold pass's 256 lanes
+    # two_blocks and five_blocks_offset with B = 2, Co = 3, so that plane and channel differ in whole and ragged chunks alike; named
+    # to sort behind the others, whose seeds are their places in the sorted names
+    "work_split_images": (2, 3, 33, 128, 5, 0),
+    "work_split_images_offset": (2, 3, 33, 128, 5, 1),
 }
 
 
