@@ -112,6 +112,40 @@ def pyramid_with_pooled(self, pyramid, pooled, size, resize):
     return pyramid + [broadcast_or_resize(pooled, size, resize)]
 
 
+def aspp_pyramid(self, top):
+    """[branch(top) for branch in self.parallel_branches], the statement every v3+ forward of the package starts with.
+
+    On a head class marked by halo_amd.hooks.use_fused_aspp_depthwise, every maximal run of 2..4 consecutive branches that are
+    separable blocks under use_fused_depthwise (the block's class carries fused_dwsep_forward) with an nn.ReLU depthwise_activate,
+    and whose depthwise halves halo_amd.dwconv.multi_fallback_reason serves together, gets those halves from one
+    halo_amd.dwconv.multi_depthwise_bn_relu call -- top is read once for the run, and the run's share of top's gradient is
+    written once -- and each output goes through halo_amd.hooks.pointwise_tail(block, y_i).  Longer runs are cut into groups of
+    at most four.  Branch order is unchanged; every other branch is called as before."""
+    if not getattr(type(self), "_halo_fused_aspp_depthwise", False):
+        return [branch(top) for branch in self.parallel_branches]
+    branches = list(self.parallel_branches)
+    from ...dwconv import MULTI_MAX, multi_depthwise_bn_relu, multi_fallback_reason
+    from ...hooks import _DWSEP_ATTRS, _inherited, fused_dwsep_forward, pointwise_tail
+
+    def eligible(m):
+        return (all(hasattr(m, a) for a in _DWSEP_ATTRS) and _inherited(type(m), "forward") is fused_dwsep_forward
+                and type(m.depthwise_activate) is nn.ReLU)
+
+    pyramid, i = [], 0
+    while i < len(branches):
+        run = []
+        while i + len(run) < len(branches) and len(run) < MULTI_MAX and eligible(branches[i + len(run)]):
+            run.append(branches[i + len(run)])
+        blocks = [(m.depthwise_conv, m.depthwise_bn, m.depthwise_activate) for m in run]
+        if len(run) >= 2 and multi_fallback_reason(top, blocks) is None:
+            pyramid += [pointwise_tail(m, y) for m, y in zip(run, multi_depthwise_bn_relu(top, blocks))]
+            i += len(run)
+        else:
+            pyramid.append(branches[i](top))
+            i += 1
+    return pyramid
+
+
 def v3plus_bottleneck(self, pyramid, pooled, resize):
     """The bottleneck of a head marked by halo_amd.hooks.use_folded_image_pooling: pyramid holds the parallel branches alone, pooled
     is global_branch's (B, Cg, 1, 1) output.  A `bottleneck` of the form Sequential(Conv2d, FrozenBatchNorm2d, nn.ReLU) inside the
@@ -197,7 +231,7 @@ def v3plus_hyper_forward(self, x, size=None):
     """forward of DepthwiseSeparableASPP_Hyper (classifier.py:486-558): the instance's own ASPP / decoder
     modules (PyTorch), optional weighted normalisation (`wn_mlp`, HFR), then the HIP tail."""
     low, top = x["low"], x["out"]
-    pyramid = [branch(top) for branch in self.parallel_branches]
+    pyramid = aspp_pyramid(self, top)
     pooled = self.global_branch(top)
     resize = device_resize(self)
     if folded_pooling(self, pooled):
@@ -229,7 +263,7 @@ def v3plus_forward(self, x, size=None):
     run on it (halo_amd.hooks.run_decoder_pair)."""
     from ...hooks import run_decoder_pair
     low, top = x["low"], x["out"]
-    pyramid = [branch(top) for branch in self.parallel_branches]
+    pyramid = aspp_pyramid(self, top)
     pooled = self.global_branch(top)
     # the mark is about the device backward's atomics: on CPU tensors, which no operator serves, every resize is the stock statement --
     # the 1 x 1 pooled map's too, whose broadcast has F.interpolate's values but sums its gradient in another order

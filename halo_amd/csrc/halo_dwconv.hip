@@ -28,6 +28,9 @@
 // plane below Ca reads its window through DwUpSrc (the resize's own taps and bilerp, evaluated per window row), the others read
 // s through DwSrc.  Same DwGeom for C = Ca + Cs, same walk, same k_dw_wsum: the bits are those of the conv over the stored
 // concatenation.  The data gradient is written to two dense tensors split at plane Ca.
+//
+// The ASPP pyramid (halo_multi_dwconv3x3_*): N dilations over one input.  The one place with LDS: a workgroup keeps a plane there
+// and runs the same walk once per dilation (the section in front of the entry points).
 #include "halo_common.hpp"
 #include "halo_devmath.hpp"
 #include "halo_softmax.hpp"
@@ -480,6 +483,206 @@ static DwCat upcat_operands(int64_t Ca, int64_t Cs, int64_t h, int64_t w, int64_
     return K;
 }
 
+// ---------------------------------------------------------------- N dilations over one LDS-resident plane (the ASPP pyramid)
+// The v3+ heads hand one tensor to three dilated blocks.  A workgroup owns one plane (b, c) at a time and keeps it in LDS:
+//   forward   the plane of x is staged once (16-byte or one-element loads); for each dilation in list order the chain walk above
+//             runs over the LDS copy -- DwSrc<DW_FWD> with `a` pointing into LDS, dw_walk_apply unchanged, so the three-row register
+//             window, the order of the 9-term sum and the roundings are the single-dilation kernel's -- and stores y_i.
+//   backward  two LDS planes.  For each dilation with a gradient, gp_i = DwSrc<DW_BWD>::at (one rounding) is staged into the first,
+//             the mirrored-tap walk reads it and writes its sum s_i into the second: the first dilation stores, every later one
+//             does acc = acc + s_i (one float32 add, the bits of torch's (gx_0 + gx_1) + gx_2).  g_x is written once from LDS.
+//             A null g_i is neither staged nor added.  No atomics, no read-modify-write of global memory.
+// A plane's items (dw_geom's column groups x chains x segments) are spread over the block by a loop.  Dilation 1 takes the
+// general window (<GW, false>): its three LDS reads per row are the same values as the <4, true> route's one load and two scalars.
+// LDS: H W floats forward, 2 H W backward, dynamic; DWM_MAX_PLANE is the plane whose two copies fill a CU's 160 KiB.
+constexpr int DWM_MAX_N = 4;
+constexpr int DWM_FWD_TPB = 512, DWM_BWD_TPB = 1024;
+constexpr int DWM_LDS_BYTES = 160 * 1024;
+constexpr int64_t DWM_MAX_PLANE = DWM_LDS_BYTES / (2 * sizeof(float));
+constexpr int64_t DWM_MAX_GRID = 1 << 20;
+
+struct DwMulti {
+    int n;
+    DwGeom G[DWM_MAX_N];
+    const float *g[DWM_MAX_N];   // backward: the gradient of y_i, null when that output was not used
+};
+
+// item `item` (below G.items) of a plane: dw_item's split without the block
+template <int GW> __device__ __forceinline__ DwItem dwm_item(const DwGeom &G, long long item)
+{
+    const int g = (int)(item % G.ngroups);
+    const long long t = item / G.ngroups;
+    const int r = (int)(t % G.nres);
+    const long long k0 = (t / G.nres) * DW_L;
+    const long long i0 = r + k0 * G.d, iend = i0 + (long long)DW_L * G.d;
+    DwItem it;
+    it.c0 = g * GW;
+    it.i0 = (int)(i0 < G.H ? i0 : G.H);
+    it.iend = (int)(iend < G.H ? iend : G.H);
+    return it;
+}
+
+// dw_walk_apply<DW_BWD, GW, false> with the result stored to, or added onto, the LDS plane `acc`
+template <int GW>
+__device__ __forceinline__ void dwm_walk_acc(const DwSrc<DW_FWD> &src, const float (&wk)[9], float *acc, bool add, const DwItem &it, const DwGeom &G)
+{
+    const int d = G.d;
+    float win[3][3 * GW];
+    src.template row<GW, false>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
+    src.template row<GW, false>(win[1], it.i0, it.c0, G.H, G.W, d);
+    for (int i = it.i0; i < it.iend; i += d) {
+        src.template row<GW, false>(win[2], i + d, it.c0, G.H, G.W, d);
+        float res[GW];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            float s = wk[0] * win[0][e];
+#pragma unroll
+            for (int k = 1; k < 9; ++k) s = __builtin_fmaf(wk[k], win[k / 3][(k % 3) * GW + e], s);
+            res[e] = s;
+        }
+        float *o = acc + (size_t)i * G.W + it.c0;
+        if constexpr (GW == 4) {
+            dw_f4 v;
+            v.x = res[0], v.y = res[1], v.z = res[2], v.w = res[3];
+            if (add) {
+                const dw_f4 a = *reinterpret_cast<const dw_f4 *>(o);
+                v.x = a.x + v.x, v.y = a.y + v.y, v.z = a.z + v.z, v.w = a.w + v.w;
+            }
+            *reinterpret_cast<dw_f4 *>(o) = v;
+        } else {
+            o[0] = add ? o[0] + res[0] : res[0];
+        }
+#pragma unroll
+        for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
+    }
+}
+
+// y (n, B, C, H, W): y[i] = relu((dw3x3_{d_i}(x) over w[i]) * scale[i] + shift[i]); GW = 4 needs W % 4 == 0 and 16-byte aligned x, y
+template <int GW>
+__global__ void __launch_bounds__(DWM_FWD_TPB) k_dwm_fwd(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ scale,
+                                                         const float *__restrict__ shift, float *__restrict__ y, DwMulti P, long long planes)
+{
+    extern __shared__ __attribute__((aligned(16))) float dwm_lds[];
+    const int hw = P.G[0].H * P.G[0].W, C = P.G[0].C;
+    for (long long plane = blockIdx.x; plane < planes; plane += gridDim.x) {
+        const int c = (int)(plane % C);
+        const size_t po = (size_t)plane * hw;
+        if constexpr (GW == 4) {
+            for (int q = threadIdx.x; q < hw / 4; q += DWM_FWD_TPB)
+                reinterpret_cast<dw_f4 *>(dwm_lds)[q] = reinterpret_cast<const dw_f4 *>(x + po)[q];
+        } else {
+            for (int q = threadIdx.x; q < hw; q += DWM_FWD_TPB) dwm_lds[q] = x[po + q];
+        }
+        __syncthreads();
+        for (int i = 0; i < P.n; ++i) {
+            const DwGeom G = P.G[i];
+            const size_t ch = (size_t)i * C + c;
+            const float sc = scale[ch], sh = shift[ch];
+            float wk[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) wk[k] = w[ch * 9 + k];
+            DwSrc<DW_FWD> src;
+            src.a = dwm_lds, src.y = nullptr, src.scale = sc;
+            float *op = y + ((size_t)i * planes + plane) * hw;
+            for (long long item = threadIdx.x; item < G.items; item += DWM_FWD_TPB) {
+                const DwItem it = dwm_item<GW>(G, item);
+                dw_walk_apply<DW_FWD, GW, false>(src, wk, sc, sh, op, it, G);
+            }
+        }
+        __syncthreads();                                   // the next plane overwrites what the walks read
+    }
+}
+
+// g_x = the sum, in list order, of dw3x3_{d_i}^T(gp_i) over the dilations whose P.g[i] is not null; GW = 4 needs W % 4 == 0 and
+// 16-byte aligned g_i, y, g_x
+template <int GW>
+__global__ void __launch_bounds__(DWM_BWD_TPB) k_dwm_bwd(const float *__restrict__ yv, const float *__restrict__ w, const float *__restrict__ scale,
+                                                         float *__restrict__ g_x, DwMulti P, long long planes)
+{
+    extern __shared__ __attribute__((aligned(16))) float dwm_lds[];
+    const int hw = P.G[0].H * P.G[0].W, C = P.G[0].C;
+    float *gp = dwm_lds, *acc = dwm_lds + hw;             // hw is a multiple of 4 on the 16-byte route
+    for (long long plane = blockIdx.x; plane < planes; plane += gridDim.x) {
+        const int c = (int)(plane % C);
+        const size_t po = (size_t)plane * hw;
+        bool add = false;
+        for (int i = 0; i < P.n; ++i) {
+            const float *gi = P.g[i];
+            if (!gi) continue;
+            const DwGeom G = P.G[i];
+            const size_t ch = (size_t)i * C + c;
+            DwSrc<DW_BWD> in;
+            in.a = gi + po, in.y = yv + ((size_t)i * planes + plane) * hw, in.scale = scale[ch];
+            if constexpr (GW == 4) {
+                for (int q = threadIdx.x; q < hw / 4; q += DWM_BWD_TPB) {
+                    float v[4];
+                    in.template at4<dw_f4>((size_t)q * 4, v);
+                    dw_f4 o;
+                    o.x = v[0], o.y = v[1], o.z = v[2], o.w = v[3];
+                    reinterpret_cast<dw_f4 *>(gp)[q] = o;
+                }
+            } else {
+                for (int q = threadIdx.x; q < hw; q += DWM_BWD_TPB) gp[q] = in.at((size_t)q);
+            }
+            __syncthreads();
+            float wk[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) wk[k] = w[ch * 9 + 8 - k];
+            DwSrc<DW_FWD> src;
+            src.a = gp, src.y = nullptr, src.scale = 0.0f;
+            for (long long item = threadIdx.x; item < G.items; item += DWM_BWD_TPB) {
+                const DwItem it = dwm_item<GW>(G, item);
+                dwm_walk_acc<GW>(src, wk, acc, add, it, G);
+            }
+            __syncthreads();                               // gp is restaged, and another thread adds onto this element next
+            add = true;
+        }
+        if constexpr (GW == 4) {
+            for (int q = threadIdx.x; q < hw / 4; q += DWM_BWD_TPB)
+                reinterpret_cast<dw_f4 *>(g_x + po)[q] = reinterpret_cast<const dw_f4 *>(acc)[q];
+        } else {
+            for (int q = threadIdx.x; q < hw; q += DWM_BWD_TPB) g_x[po + q] = acc[q];
+        }
+        // no barrier: the next plane's first walk writes acc only behind the barrier that follows its staging
+    }
+}
+
+static int dwm_check(const char *who, int64_t B, int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d)
+{
+    if (n < 2 || n > DWM_MAX_N) return fail(HALO_E_ARG, "%s: %lld dilations, 2 to %d are served", who, (long long)n, DWM_MAX_N);
+    if (!d) return fail(HALO_E_ARG, "%s: null argument", who);
+    for (int64_t i = 0; i < n; ++i)
+        if (int rc = dw_check(who, B, C, H, W, d[i])) return rc;
+    return HALO_OK;
+}
+
+static int dwm_plane_check(const char *who, int64_t H, int64_t W)
+{
+    if (H * W > DWM_MAX_PLANE)
+        return fail(HALO_E_UNSUPPORTED, "%s: plane of %lld x %lld = %lld elements, two copies of at most %lld fit the LDS", who, (long long)H,
+                    (long long)W, (long long)(H * W), (long long)DWM_MAX_PLANE);
+    return HALO_OK;
+}
+
+static DwMulti dwm_operands(int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, int gw)
+{
+    DwMulti P;
+    P.n = (int)n;
+    for (int i = 0; i < DWM_MAX_N; ++i) {
+        P.G[i] = dw_geom(C, H, W, d[i < n ? i : 0], gw);
+        P.g[i] = nullptr;
+    }
+    return P;
+}
+
+// the launch's LDS: above the default 64 KiB the limit is raised first (once per kernel and device)
+static int dwm_raise_lds(const char *who,LdsLimitSeen &seen, const void *kernel, size_t bytes)
+{
+    if (bytes > 64 * 1024 && !raise_lds_limit(seen, kernel, DWM_LDS_BYTES))
+        return fail(HALO_E_LAUNCH, "%s: the device refused %d bytes of LDS per workgroup", who, DWM_LDS_BYTES);
+    return HALO_OK;
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -605,5 +808,60 @@ extern "C" int halo_upcat_dwconv3x3_affine_relu_bwd_weight(const float *g, const
     if (vec) hipLaunchKernelGGL((k_dw_upcat_wpart<4>), gr, bl, 0, st, g, y, a, s, scale, part, G, K);
     else hipLaunchKernelGGL((k_dw_upcat_wpart<1>), gr, bl, 0, st, g, y, a, s, scale, part, G, K);
     hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
+    return check_launch(who);
+}
+
+extern "C" int64_t halo_multi_dwconv_max_plane(void) { return DWM_MAX_PLANE; }
+
+extern "C" int halo_multi_dwconv3x3_affine_relu_fwd(const float *x, const float *w, const float *scale, const float *shift, float *y, int64_t B,
+                                                    int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, void *stream)
+{
+    const char *who = "halo_multi_dwconv3x3_affine_relu_fwd";
+    if (int rc = dwm_check(who, B, C, H, W, n, d)) return rc;
+    if (!x || !w || !scale || !shift || !y) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (int rc = dwm_plane_check(who, H, W)) return rc;
+    const bool vec = dw_vec(W, x, y, nullptr, nullptr);
+    const DwMulti P = dwm_operands(C, H, W, n, d, vec ? 4 : 1);
+    const int64_t planes = B * C;
+    const dim3 gr((unsigned)(planes < DWM_MAX_GRID ? planes : DWM_MAX_GRID)), bl(DWM_FWD_TPB);
+    const size_t lds = (size_t)(H * W) * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    static LdsLimitSeen seen4, seen1;
+    if (vec) {
+        if (int rc = dwm_raise_lds(who, seen4, (const void *)k_dwm_fwd<4>, lds)) return rc;
+        hipLaunchKernelGGL((k_dwm_fwd<4>), gr, bl, lds, st, x, w, scale, shift, y, P, (long long)planes);
+    } else {
+        if (int rc = dwm_raise_lds(who, seen1, (const void *)k_dwm_fwd<1>, lds)) return rc;
+        hipLaunchKernelGGL((k_dwm_fwd<1>), gr, bl, lds, st, x, w, scale, shift, y, P, (long long)planes);
+    }
+    return check_launch(who);
+}
+
+extern "C" int halo_multi_dwconv3x3_affine_relu_bwd_data(const float *const *g, const float *y, const float *w, const float *scale, float *g_x,
+                                                         int64_t B, int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, void *stream)
+{
+    const char *who = "halo_multi_dwconv3x3_affine_relu_bwd_data";
+    if (int rc = dwm_check(who, B, C, H, W, n, d)) return rc;
+    if (!g || !y || !w || !scale || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
+    uintptr_t bits = 0;
+    bool any = false;
+    for (int64_t i = 0; i < n; ++i) any = any || g[i], bits |= (uintptr_t)g[i];
+    if (!any) return fail(HALO_E_ARG, "%s: every gradient is null", who);
+    if (int rc = dwm_plane_check(who, H, W)) return rc;
+    const bool vec = dw_vec(W, (const void *)bits, y, g_x, nullptr);
+    DwMulti P = dwm_operands(C, H, W, n, d, vec ? 4 : 1);
+    for (int64_t i = 0; i < n; ++i) P.g[i] = g[i];
+    const int64_t planes = B * C;
+    const dim3 gr((unsigned)(planes < DWM_MAX_GRID ? planes : DWM_MAX_GRID)), bl(DWM_BWD_TPB);
+    const size_t lds = (size_t)(H * W) * 2 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    static LdsLimitSeen seen4, seen1;
+    if (vec) {
+        if (int rc = dwm_raise_lds(who, seen4, (const void *)k_dwm_bwd<4>, lds)) return rc;
+        hipLaunchKernelGGL((k_dwm_bwd<4>), gr, bl, lds, st, y, w, scale, g_x, P, (long long)planes);
+    } else {
+        if (int rc = dwm_raise_lds(who, seen1, (const void *)k_dwm_bwd<1>, lds)) return rc;
+        hipLaunchKernelGGL((k_dwm_bwd<1>), gr, bl, lds, st, y, w, scale, g_x, P, (long long)planes);
+    }
     return check_launch(who);
 }

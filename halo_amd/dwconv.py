@@ -26,6 +26,9 @@ concatenated tensor: the kernel reads its window from a (interpolated in place, 
 backward keeps a, s and y, recomputes the conv's input for the weight gradient and writes the data gradient as two dense tensors,
 the first of which halo_bilinear_upsample_bwd turns into g_a.  Its results are those of depthwise_bn_relu over the stored
 concatenation, bit for bit; outside its envelope (upcat_fallback_reason) it runs that composition.
+
+The ASPP pyramid hands one tensor to three such blocks.  `multi_depthwise_bn_relu(x, blocks)` computes their depthwise halves in one
+pass each way over a plane held in LDS, with the bits of one depthwise_bn_relu per block (the section at the end of this file).
 """
 import torch
 import torch.nn as nn
@@ -266,4 +269,114 @@ def upsample_cat_depthwise_bn_relu(a, s, conv, bn, act=None):
     return _UpCatDepthwiseBnReluFn.apply(a.contiguous(), s.contiguous(), conv.weight.contiguous(), scale, shift)
 
 
-__all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift", "upsample_cat_depthwise_bn_relu", "upcat_fallback_reason"]
+# ---------------------------------------------------------------- the ASPP pyramid: N dilations over one input
+# Both v3+ heads hand one tensor to three dilated blocks.  multi_depthwise_bn_relu(x, blocks) runs their depthwise halves as one
+# pass each way (halo_multi_dwconv3x3_* of halo_dwconv.hip: a workgroup keeps a plane in LDS): x is read once for the N outputs,
+# and the N input gradients are added in LDS and written once.  Every result carries the bits of the composition
+#     y_i = depthwise_bn_relu(x, conv_i, bn_i);  g_x = ((gx_0 + gx_1) + gx_2) ... (torch float32 adds in list order, the outputs
+#     that were not used left out);  g_w_i: the same halo_dwconv3x3_affine_relu_bwd_weight call over the same operands
+# so the fallback, which is that composition, never changes a bit.
+
+launches = {"multi_fwd": 0, "multi_bwd": 0}
+MULTI_MIN, MULTI_MAX = 2, 4                                          # DWM_MAX_N of halo_dwconv.hip
+# A speed rule only (both sides return the same bits; the GPU tests switch it off): the smallest input timed against the
+# composition, 1 x 2048 x 80 x 160 (profiles/r23_time_aspp_depthwise.txt).  Nothing smaller was measured, so nothing smaller is served.
+MULTI_MIN_ELEMENTS = 1 * 2048 * 80 * 160
+
+
+def multi_max_plane():
+    """the largest H * W the multi-dilation passes serve: two float32 planes of it fill a CU's LDS (a host-only query)"""
+    return int(_lib.lib().halo_multi_dwconv_max_plane())
+
+
+def multi_fallback_reason(x, blocks):
+    """why multi_depthwise_bn_relu(x, blocks) runs one depthwise_bn_relu per block (None: the fused passes serve it).  blocks: a
+    sequence of (conv, bn) or (conv, bn, act).  Reads no device memory."""
+    blocks = [tuple(b) for b in blocks]
+    if not MULTI_MIN <= len(blocks) <= MULTI_MAX:
+        return "%d blocks, %d to %d are served" % (len(blocks), MULTI_MIN, MULTI_MAX)
+    if any(len(b) not in (2, 3) for b in blocks):
+        return "a block is not (conv, bn) or (conv, bn, act)"
+    channels = [getattr(b[0], "in_channels", None) for b in blocks]
+    if len(set(channels)) != 1:
+        return "the blocks' channel counts differ: %s" % (channels,)
+    for i, b in enumerate(blocks):
+        why = fallback_reason(x, b[0], b[1])
+        if why is not None:
+            return "block %d: %s" % (i, why)
+    B, C, H, W = x.shape
+    if H * W > multi_max_plane():
+        return "plane of %d x %d = %d elements, above the %d that fit the LDS twice" % (H, W, H * W, multi_max_plane())
+    if B * C * H * W < MULTI_MIN_ELEMENTS:
+        return "%d elements, fewer than MULTI_MIN_ELEMENTS = %d (a speed rule: nothing smaller was timed)" % (B * C * H * W, MULTI_MIN_ELEMENTS)
+    return None
+
+
+class _MultiDepthwiseBnReluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, dil, *ws):
+        import ctypes
+        B, C, H, W = x.shape
+        n = len(ws)
+        L = _lib.lib()
+        w = torch.stack([wi.reshape(C, 9) for wi in ws])
+        y = torch.empty((n, B, C, H, W), dtype=torch.float32, device=x.device)
+        _lib.check(L.halo_multi_dwconv3x3_affine_relu_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W, n,
+                                                          (ctypes.c_int64 * n)(*dil), _lib.stream_ptr(x.device)),
+                   "halo_multi_dwconv3x3_affine_relu_fwd")
+        launches["multi_fwd"] += 1
+        ctx.save_for_backward(x, y, w, scale)
+        ctx.dil = dil
+        ctx.set_materialize_grads(False)
+        return tuple(y.unbind(0))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        import ctypes
+        x, y, w, scale = ctx.saved_tensors
+        B, C, H, W = x.shape
+        n, dil = len(gs), ctx.dil
+        L = _lib.lib()
+        st = _lib.stream_ptr(x.device)
+        gs = [None if g is None else g.to(device=x.device, dtype=torch.float32).contiguous() for g in gs]
+        gx, gws = None, [None] * n
+        if all(g is None for g in gs):
+            return (None,) * (4 + n)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            ptrs = (ctypes.c_void_p * n)(*[None if g is None else g.data_ptr() for g in gs])
+            _lib.check(L.halo_multi_dwconv3x3_affine_relu_bwd_data(ptrs, _lib.ptr(y), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(gx), B, C, H, W, n,
+                                                                   (ctypes.c_int64 * n)(*dil), st), "halo_multi_dwconv3x3_affine_relu_bwd_data")
+            launches["multi_bwd"] += 1
+        for i, g in enumerate(gs):
+            if g is None or not ctx.needs_input_grad[4 + i]:
+                continue
+            nws = L.halo_dwconv_workspace_bytes(B, C, H, W, dil[i])
+            ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=x.device)
+            gws[i] = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
+            _lib.check(L.halo_dwconv3x3_affine_relu_bwd_weight(_lib.ptr(g), _lib.ptr(y[i]), _lib.ptr(x), _lib.ptr(scale[i]), _lib.ptr(gws[i]), B, C,
+                                                               H, W, dil[i], _lib.ptr(ws), ws.numel() * 8, st),
+                       "halo_dwconv3x3_affine_relu_bwd_weight")
+        return (gx, None, None, None) + tuple(gws)
+
+
+def multi_depthwise_bn_relu(x, blocks):
+    """(relu(bn_i(conv_i(x))) for every block) of N = 2..4 depthwise 3x3 convs with frozen / eval-mode norms over one x (B, C, H, W):
+    a tuple of N tensors.  blocks: a sequence of (conv, bn) or (conv, bn, act).  Differentiable once w.r.t. x and every
+    conv.weight; one launch forward, one for g_x, one halo_dwconv3x3_affine_relu_bwd_weight per weight.  The bits are those of
+    tuple(depthwise_bn_relu(x, *block) for block in blocks) and of its autograd (g_x added in list order), which is what runs
+    outside the served envelope (multi_fallback_reason)."""
+    blocks = [tuple(b) for b in blocks]
+    if multi_fallback_reason(x, blocks) is not None:
+        # called last block first: the engine runs the nodes made last first and adds the gradients of x as they arrive, so the
+        # composition's g_x is ((gx_0 + gx_1) + gx_2) ... as well
+        return tuple(reversed([depthwise_bn_relu(x, *b) for b in reversed(blocks)]))
+    pairs = [scale_shift(b[1]) for b in blocks]
+    scale, shift = torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
+    dil = tuple(int(_pair(b[0].dilation)[0]) for b in blocks)
+    return _MultiDepthwiseBnReluFn.apply(x.contiguous(), scale, shift, dil, *[b[0].weight.contiguous() for b in blocks])
+
+
+__all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift", "upsample_cat_depthwise_bn_relu", "upcat_fallback_reason",
+           "multi_depthwise_bn_relu", "multi_fallback_reason", "multi_max_plane", "launches"]

@@ -286,10 +286,10 @@ def use_fused_training_losses(learner_cls):
 # kept as `_unfused_forward`.  Neither install() nor the existing forward changes.
 
 def fused_v3plus_hyper_forward(self, x, size=None):
-    from .core.models.classifier import _tail_modules, broadcast_or_resize, device_resize, folded_pooling, hyper_head_tail, v3plus_decoder
+    from .core.models.classifier import _tail_modules, aspp_pyramid, broadcast_or_resize, device_resize, folded_pooling, hyper_head_tail, v3plus_decoder
     from .hfr import weighted_normalize
     low, top = x["low"], x["out"]
-    pyramid = [branch(top) for branch in self.parallel_branches]
+    pyramid = aspp_pyramid(self, top)
     pooled = self.global_branch(top)
     resize = device_resize(self)
     if folded_pooling(self, pooled):
@@ -416,6 +416,31 @@ def use_fused_decoder_front(head_cls):
         raise TypeError("use_fused_decoder_front: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
                         "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
     head_cls._halo_fused_decoder_front = True
+    return head_cls
+
+
+# ---------------------------------------------------------------- the ASPP pyramid's dilated depthwise halves in one pass each way
+# Both v3+ forwards hand the backbone's output to parallel_branches, three of which are dilated separable blocks whose depthwise
+# halves each read it, and whose backward each write a gradient of its size that the autograd engine then adds.
+# `use_fused_aspp_depthwise(head_cls)` marks a head class that carries one of the package's v3+ forwards; its instances run such
+# neighbours' depthwise halves as halo_amd.dwconv.multi_depthwise_bn_relu (core.models.classifier.aspp_pyramid: the conditions and
+# the fallback).  A class attribute like use_fused_decoder_front's: opt-in, not bound by install(), composes with the other hooks
+# in any order; parameters, module names and state_dict() are untouched.  It acts on blocks under use_fused_depthwise only.
+
+def use_fused_aspp_depthwise(head_cls):
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward, fused_v3plus_hyper_forward or v3plus_forward) so that
+    consecutive dilated separable blocks of parallel_branches under use_fused_depthwise run their depthwise halves as one HIP pass
+    forward and one for the input gradient.  Returns the class.  Idempotent.  The marked head returns the bits of the same head
+    under use_fused_depthwise alone: both outputs and every parameter gradient.  Only the gradient of the backbone's output is not
+    bit-equal: the pass adds the blocks' shares first and the engine adds the remaining branches' onto that, another association
+    of the same float32 terms t_i -- two summation orders of five terms differ by at most 2 gamma_4 sum |t_i|, gamma_4 =
+    4u / (1 - 4u), u = 2^-24."""
+    if not isinstance(head_cls, type):
+        raise TypeError("use_fused_aspp_depthwise: expected a class, got %r" % (head_cls,))
+    if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
+        raise TypeError("use_fused_aspp_depthwise: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
+                        "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
+    head_cls._halo_fused_aspp_depthwise = True
     return head_cls
 
 

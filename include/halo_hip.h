@@ -427,6 +427,25 @@ int halo_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, const 
                                           int64_t C, int64_t H, int64_t W, int64_t d, void *workspace, size_t workspace_bytes,
                                           void *stream);
 
+/* ---- the ASPP pyramid: n dilated depthwise 3x3 conv + frozen norm + ReLU over one input, one pass each way ----
+ *  x, g_x, every g[i] (B, C, H, W) f32 dense NCHW; y (n, B, C, H, W) f32 dense, y[i] the output of dilation d[i]; w (n, C, 9),
+ *  scale, shift (n, C) f32; d a HOST array of n dilations, 2 <= n <= 4, in any order, repeats allowed; g a HOST array of n device
+ *  pointers (they travel in the kernel's arguments), NULL for an output that has no gradient, at least one not NULL.
+ *    y[i] = the forward above over (x, w[i], scale[i], shift[i], d[i]): its bits.
+ *    g_x  = ((gx_0 + gx_1) + gx_2) ..., gx_i the bwd_data above over (g[i], y[i], w[i], scale[i], d[i]), float32 adds in list order,
+ *           the NULL entries left out: the bits of that composition.
+ *  A workgroup keeps one plane in LDS (forward: x, read from memory once; backward: gp_i and the running sum, g_x written once),
+ *  so H * W <= halo_multi_dwconv_max_plane() (a host-only query: no device call).  No atomics.  16-byte accesses when W % 4 == 0
+ *  and x, y (fwd) or every g[i], y, g_x (bwd) are 16-byte aligned, one element per lane otherwise: the same bits.  The weight
+ *  gradients are n calls of halo_dwconv3x3_affine_relu_bwd_weight.  HALO_E_ARG: n outside 2..4, a missing pointer, every g[i]
+ *  NULL, an empty shape, a d[i] < 1; HALO_E_UNSUPPORTED: the size limits above, a plane above the query's; HALO_E_LAUNCH: the device
+ *  refused the LDS size.  Every check comes before any launch. */
+int64_t halo_multi_dwconv_max_plane(void);
+int halo_multi_dwconv3x3_affine_relu_fwd(const float *x, const float *w, const float *scale, const float *shift, float *y, int64_t B,
+                                         int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, void *stream);
+int halo_multi_dwconv3x3_affine_relu_bwd_data(const float *const *g, const float *y, const float *w, const float *scale, float *g_x,
+                                              int64_t B, int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, void *stream);
+
 /* ---- the front of the v3+ decoder: resize + concat + depthwise 3x3 conv + frozen norm + ReLU in one pass ----
  *  a (B, Ca, h, w), s (B, Cs, H, W) with H >= h, W >= w, y and g (B, Ca + Cs, H, W), g_up (B, Ca, H, W), g_s (B, Cs, H, W): f32 dense
  *  NCHW; w (Ca + Cs, 1, 3, 3), scale, shift (Ca + Cs) f32; dilation = padding = 1.
