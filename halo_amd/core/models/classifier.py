@@ -123,27 +123,93 @@ def aspp_pyramid(self, top):
     at most four.  Branch order is unchanged; every other branch is called as before."""
     if not getattr(type(self), "_halo_fused_aspp_depthwise", False):
         return [branch(top) for branch in self.parallel_branches]
+    return [y for segment in _pyramid_segments(self, top) for y in _run_segment(segment, top)]
+
+
+def _pyramid_segments(self, top):
+    """parallel_branches of a head marked by use_fused_aspp_depthwise, cut in branch order into aspp_pyramid's segments: (run, blocks)
+    for a run that multi_depthwise_bn_relu serves over `top`, ([branch], None) for every other branch.  Calls no branch."""
     branches = list(self.parallel_branches)
-    from ...dwconv import MULTI_MAX, multi_depthwise_bn_relu, multi_fallback_reason
-    from ...hooks import _DWSEP_ATTRS, _inherited, fused_dwsep_forward, pointwise_tail
+    from ...dwconv import MULTI_MAX, multi_fallback_reason
+    from ...hooks import _DWSEP_ATTRS, _inherited, fused_dwsep_forward
 
     def eligible(m):
         return (all(hasattr(m, a) for a in _DWSEP_ATTRS) and _inherited(type(m), "forward") is fused_dwsep_forward
                 and type(m.depthwise_activate) is nn.ReLU)
 
-    pyramid, i = [], 0
+    segments, i = [], 0
     while i < len(branches):
         run = []
         while i + len(run) < len(branches) and len(run) < MULTI_MAX and eligible(branches[i + len(run)]):
             run.append(branches[i + len(run)])
         blocks = [(m.depthwise_conv, m.depthwise_bn, m.depthwise_activate) for m in run]
         if len(run) >= 2 and multi_fallback_reason(top, blocks) is None:
-            pyramid += [pointwise_tail(m, y) for m, y in zip(run, multi_depthwise_bn_relu(top, blocks))]
+            segments.append((run, blocks))
             i += len(run)
         else:
-            pyramid.append(branches[i](top))
+            segments.append(([branches[i]], None))
             i += 1
-    return pyramid
+    return segments
+
+
+def _run_segment(segment, top):
+    """the outputs of one of _pyramid_segments' segments over `top`"""
+    from ...dwconv import multi_depthwise_bn_relu
+    from ...hooks import pointwise_tail
+    run, blocks = segment
+    if blocks is None:
+        return [run[0](top)]
+    return [pointwise_tail(m, y) for m, y in zip(run, multi_depthwise_bn_relu(top, blocks))]
+
+
+def _plane_mean_branch(branch):
+    """whether `branch` is an nn.Sequential, called as one, that starts with an nn.AdaptiveAvgPool2d of output size 1 and carries no
+    forward hooks: halo_amd.fanout.plane_mean can stand in for that child"""
+    if not isinstance(branch, nn.Sequential) or type(branch).forward is not nn.Sequential.forward or "forward" in branch.__dict__ or len(branch) == 0:
+        return False
+    pool = branch[0]
+    if type(pool) is not nn.AdaptiveAvgPool2d or "forward" in pool.__dict__ or pool.output_size not in (1, (1, 1), [1, 1]):
+        return False
+    return not any(m._forward_hooks or m._forward_pre_hooks for m in (branch, pool))
+
+
+def pooled_aspp_pyramid(self, top):
+    """(aspp_pyramid(self, top), self.global_branch(top)): the two statements every v3+ forward of the package starts with, and
+    exactly those on a head class that halo_amd.hooks.use_joined_aspp_gradients has not marked.
+
+    A head marked by it and by use_fused_aspp_depthwise, whose first served run of dilated blocks
+    halo_amd.fanout.fan_fallback_reason accepts with one further reader per other segment of the pyramid (a branch, or a later
+    served run) and one for global_branch, runs that run through halo_amd.fanout.fan_depthwise_bn_relu: every other segment reads
+    one of the aliases of top it returns, in branch order, global_branch the last, and top's gradient is written once, by that
+    node's pass.  A global_branch of the form Sequential(AdaptiveAvgPool2d(1), ...) without forward hooks has
+    halo_amd.fanout.plane_mean stand in for the pool -- its gradient then reaches the pass as one value per plane -- and its
+    remaining children called in order; any other global_branch is called whole on its alias.  Outputs and parameter gradients are
+    those of the head under use_fused_aspp_depthwise alone, bit for bit."""
+    cls = type(self)
+    if getattr(cls, "_halo_joined_aspp_gradients", False) and getattr(cls, "_halo_fused_aspp_depthwise", False):
+        from ...fanout import fan_depthwise_bn_relu, fan_fallback_reason, plane_mean
+        from ...hooks import pointwise_tail
+        segments = _pyramid_segments(self, top)
+        served = next((k for k, s in enumerate(segments) if s[1] is not None), None)
+        if served is not None and fan_fallback_reason(top, segments[served][1], len(segments)) is None:
+            ys, xs = fan_depthwise_bn_relu(top, segments[served][1], len(segments))
+            xs, pyramid = list(xs), []
+            for k, segment in enumerate(segments):
+                if k == served:
+                    pyramid += [pointwise_tail(m, y) for m, y in zip(segment[0], ys)]
+                else:
+                    pyramid += _run_segment(segment, xs.pop(0))
+            pooled = xs.pop(0)
+            if _plane_mean_branch(self.global_branch):
+                pooled = plane_mean(pooled)
+                for child in list(self.global_branch)[1:]:
+                    pooled = child(pooled)
+            else:
+                pooled = self.global_branch(pooled)
+            return pyramid, pooled
+    pyramid = aspp_pyramid(self, top)
+    pooled = self.global_branch(top)
+    return pyramid, pooled
 
 
 def v3plus_bottleneck(self, pyramid, pooled, resize):
@@ -231,8 +297,7 @@ def v3plus_hyper_forward(self, x, size=None):
     """forward of DepthwiseSeparableASPP_Hyper (classifier.py:486-558): the instance's own ASPP / decoder
     modules (PyTorch), optional weighted normalisation (`wn_mlp`, HFR), then the HIP tail."""
     low, top = x["low"], x["out"]
-    pyramid = aspp_pyramid(self, top)
-    pooled = self.global_branch(top)
+    pyramid, pooled = pooled_aspp_pyramid(self, top)
     resize = device_resize(self)
     if folded_pooling(self, pooled):
         dec = v3plus_decoder(self, pyramid, low, resize, pooled=pooled)
@@ -263,8 +328,7 @@ def v3plus_forward(self, x, size=None):
     run on it (halo_amd.hooks.run_decoder_pair)."""
     from ...hooks import run_decoder_pair
     low, top = x["low"], x["out"]
-    pyramid = aspp_pyramid(self, top)
-    pooled = self.global_branch(top)
+    pyramid, pooled = pooled_aspp_pyramid(self, top)
     # the mark is about the device backward's atomics: on CPU tensors, which no operator serves, every resize is the stock statement --
     # the 1 x 1 pooled map's too, whose broadcast has F.interpolate's values but sums its gradient in another order
     resize = device_resize(self) if top.is_cuda else None

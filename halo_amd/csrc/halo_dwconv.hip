@@ -593,6 +593,48 @@ __global__ void __launch_bounds__(DWM_FWD_TPB) k_dwm_fwd(const float *__restrict
     }
 }
 
+// One plane of the backward: for each dilation whose P.g[i] is not null, gp_i is staged into `gp` and the mirrored-tap walk stores
+// (first) or adds (later) its sum into `acc`, in list order.  Ends behind a barrier: acc is complete for every thread.
+template <int GW>
+__device__ __forceinline__ void dwm_bwd_plane(const float *__restrict__ yv, const float *__restrict__ w, const float *__restrict__ scale,
+                                              const DwMulti &P, long long planes, long long plane, int hw, int C, float *gp, float *acc)
+{
+    const int c = (int)(plane % C);
+    const size_t po = (size_t)plane * hw;
+    bool add = false;
+    for (int i = 0; i < P.n; ++i) {
+        const float *gi = P.g[i];
+        if (!gi) continue;
+        const DwGeom G = P.G[i];
+        const size_t ch = (size_t)i * C + c;
+        DwSrc<DW_BWD> in;
+        in.a = gi + po, in.y = yv + ((size_t)i * planes + plane) * hw, in.scale = scale[ch];
+        if constexpr (GW == 4) {
+            for (int q = threadIdx.x; q < hw / 4; q += DWM_BWD_TPB) {
+                float v[4];
+                in.template at4<dw_f4>((size_t)q * 4, v);
+                dw_f4 o;
+                o.x = v[0], o.y = v[1], o.z = v[2], o.w = v[3];
+                reinterpret_cast<dw_f4 *>(gp)[q] = o;
+            }
+        } else {
+            for (int q = threadIdx.x; q < hw; q += DWM_BWD_TPB) gp[q] = in.at((size_t)q);
+        }
+        __syncthreads();
+        float wk[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[k] = w[ch * 9 + 8 - k];
+        DwSrc<DW_FWD> src;
+        src.a = gp, src.y = nullptr, src.scale = 0.0f;
+        for (long long item = threadIdx.x; item < G.items; item += DWM_BWD_TPB) {
+            const DwItem it = dwm_item<GW>(G, item);
+            dwm_walk_acc<GW>(src, wk, acc, add, it, G);
+        }
+        __syncthreads();                               // gp is restaged, and another thread adds onto this element next
+        add = true;
+    }
+}
+
 // g_x = the sum, in list order, of dw3x3_{d_i}^T(gp_i) over the dilations whose P.g[i] is not null; GW = 4 needs W % 4 == 0 and
 // 16-byte aligned g_i, y, g_x
 template <int GW>
@@ -603,40 +645,8 @@ __global__ void __launch_bounds__(DWM_BWD_TPB) k_dwm_bwd(const float *__restrict
     const int hw = P.G[0].H * P.G[0].W, C = P.G[0].C;
     float *gp = dwm_lds, *acc = dwm_lds + hw;             // hw is a multiple of 4 on the 16-byte route
     for (long long plane = blockIdx.x; plane < planes; plane += gridDim.x) {
-        const int c = (int)(plane % C);
         const size_t po = (size_t)plane * hw;
-        bool add = false;
-        for (int i = 0; i < P.n; ++i) {
-            const float *gi = P.g[i];
-            if (!gi) continue;
-            const DwGeom G = P.G[i];
-            const size_t ch = (size_t)i * C + c;
-            DwSrc<DW_BWD> in;
-            in.a = gi + po, in.y = yv + ((size_t)i * planes + plane) * hw, in.scale = scale[ch];
-            if constexpr (GW == 4) {
-                for (int q = threadIdx.x; q < hw / 4; q += DWM_BWD_TPB) {
-                    float v[4];
-                    in.template at4<dw_f4>((size_t)q * 4, v);
-                    dw_f4 o;
-                    o.x = v[0], o.y = v[1], o.z = v[2], o.w = v[3];
-                    reinterpret_cast<dw_f4 *>(gp)[q] = o;
-                }
-            } else {
-                for (int q = threadIdx.x; q < hw; q += DWM_BWD_TPB) gp[q] = in.at((size_t)q);
-            }
-            __syncthreads();
-            float wk[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) wk[k] = w[ch * 9 + 8 - k];
-            DwSrc<DW_FWD> src;
-            src.a = gp, src.y = nullptr, src.scale = 0.0f;
-            for (long long item = threadIdx.x; item < G.items; item += DWM_BWD_TPB) {
-                const DwItem it = dwm_item<GW>(G, item);
-                dwm_walk_acc<GW>(src, wk, acc, add, it, G);
-            }
-            __syncthreads();                               // gp is restaged, and another thread adds onto this element next
-            add = true;
-        }
+        dwm_bwd_plane<GW>(yv, w, scale, P, planes, plane, hw, C, gp, acc);
         if constexpr (GW == 4) {
             for (int q = threadIdx.x; q < hw / 4; q += DWM_BWD_TPB)
                 reinterpret_cast<dw_f4 *>(g_x + po)[q] = reinterpret_cast<const dw_f4 *>(acc)[q];
@@ -644,6 +654,59 @@ __global__ void __launch_bounds__(DWM_BWD_TPB) k_dwm_bwd(const float *__restrict
             for (int q = threadIdx.x; q < hw; q += DWM_BWD_TPB) g_x[po + q] = acc[q];
         }
         // no barrier: the next plane's first walk writes acc only behind the barrier that follows its staging
+    }
+}
+
+// The fan-out variant: x has further readers whose gradients e_0 .. e_{m-1} join the sum where k_dwm_bwd copies acc to g_x,
+//     g_x = ((acc + e_0) + e_1) ...   float32 adds in list order, a null e_j left out
+// dense[j]: e_j is (B, C, H, W); otherwise (B, C), one value per plane, e_j[plane] at every pixel.  No LDS beyond k_dwm_bwd's.
+constexpr int DWM_MAX_FAN = 4;
+struct DwFan {
+    const float *e[DWM_MAX_FAN];   // null: left out
+    int dense[DWM_MAX_FAN];
+};
+
+// GW = 4 needs, beyond k_dwm_bwd's conditions, every dense e_j 16-byte aligned
+template <int GW>
+__global__ void __launch_bounds__(DWM_BWD_TPB) k_dwm_fan_bwd(const float *__restrict__ yv, const float *__restrict__ w, const float *__restrict__ scale,
+                                                             float *__restrict__ g_x, DwMulti P, DwFan F, long long planes)
+{
+    extern __shared__ __attribute__((aligned(16))) float dwm_lds[];
+    const int hw = P.G[0].H * P.G[0].W, C = P.G[0].C;
+    float *gp = dwm_lds, *acc = dwm_lds + hw;
+    for (long long plane = blockIdx.x; plane < planes; plane += gridDim.x) {
+        const size_t po = (size_t)plane * hw;
+        dwm_bwd_plane<GW>(yv, w, scale, P, planes, plane, hw, C, gp, acc);
+        float ep[DWM_MAX_FAN];                             // the per-plane addends' values of this plane
+#pragma unroll
+        for (int j = 0; j < DWM_MAX_FAN; ++j) ep[j] = (F.e[j] && !F.dense[j]) ? F.e[j][plane] : 0.0f;
+        if constexpr (GW == 4) {
+            for (int q = threadIdx.x; q < hw / 4; q += DWM_BWD_TPB) {
+                dw_f4 v = reinterpret_cast<const dw_f4 *>(acc)[q];
+#pragma unroll
+                for (int j = 0; j < DWM_MAX_FAN; ++j) {
+                    if (!F.e[j]) continue;
+                    if (F.dense[j]) {
+                        const dw_f4 a = reinterpret_cast<const dw_f4 *>(F.e[j] + po)[q];
+                        v.x = v.x + a.x, v.y = v.y + a.y, v.z = v.z + a.z, v.w = v.w + a.w;
+                    } else {
+                        v.x = v.x + ep[j], v.y = v.y + ep[j], v.z = v.z + ep[j], v.w = v.w + ep[j];
+                    }
+                }
+                reinterpret_cast<dw_f4 *>(g_x + po)[q] = v;
+            }
+        } else {
+            for (int q = threadIdx.x; q < hw; q += DWM_BWD_TPB) {
+                float v = acc[q];
+#pragma unroll
+                for (int j = 0; j < DWM_MAX_FAN; ++j) {
+                    if (!F.e[j]) continue;
+                    v = v + (F.dense[j] ? F.e[j][po + q] : ep[j]);
+                }
+                g_x[po + q] = v;
+            }
+        }
+        // no barrier: as in k_dwm_bwd
     }
 }
 
@@ -862,6 +925,44 @@ extern "C" int halo_multi_dwconv3x3_affine_relu_bwd_data(const float *const *g, 
     } else {
         if (int rc = dwm_raise_lds(who, seen1, (const void *)k_dwm_bwd<1>, lds)) return rc;
         hipLaunchKernelGGL((k_dwm_bwd<1>), gr, bl, lds, st, y, w, scale, g_x, P, (long long)planes);
+    }
+    return check_launch(who);
+}
+
+extern "C" int halo_fan_dwconv3x3_affine_relu_bwd_data(const float *const *g, const float *y, const float *w, const float *scale, float *g_x,
+                                                       int64_t B, int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, int64_t m,
+                                                       const float *const *e, const int32_t *e_plane, void *stream)
+{
+    const char *who = "halo_fan_dwconv3x3_affine_relu_bwd_data";
+    if (int rc = dwm_check(who, B, C, H, W, n, d)) return rc;
+    if (!g || !y || !w || !scale || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (m < 0 || m > DWM_MAX_FAN) return fail(HALO_E_ARG, "%s: %lld extra addends, 0 to %d are served", who, (long long)m, DWM_MAX_FAN);
+    if (m > 0 && (!e || !e_plane)) return fail(HALO_E_ARG, "%s: null argument", who);
+    uintptr_t bits = 0;
+    bool any = false;
+    for (int64_t i = 0; i < n; ++i) any = any || g[i], bits |= (uintptr_t)g[i];
+    if (!any) return fail(HALO_E_ARG, "%s: every gradient is null", who);
+    if (int rc = dwm_plane_check(who, H, W)) return rc;
+    DwFan F;
+    for (int j = 0; j < DWM_MAX_FAN; ++j) {
+        F.e[j] = j < m ? e[j] : nullptr;
+        F.dense[j] = j < m ? e_plane[j] == 0 : 0;
+        if (F.dense[j]) bits |= (uintptr_t)F.e[j];         // a per-plane addend is read one float at a time on either route
+    }
+    const bool vec = dw_vec(W, (const void *)bits, y, g_x, nullptr);
+    DwMulti P = dwm_operands(C, H, W, n, d, vec ? 4 : 1);
+    for (int64_t i = 0; i < n; ++i) P.g[i] = g[i];
+    const int64_t planes = B * C;
+    const dim3 gr((unsigned)(planes < DWM_MAX_GRID ? planes : DWM_MAX_GRID)), bl(DWM_BWD_TPB);
+    const size_t lds = (size_t)(H * W) * 2 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    static LdsLimitSeen seen4, seen1;
+    if (vec) {
+        if (int rc = dwm_raise_lds(who, seen4, (const void *)k_dwm_fan_bwd<4>, lds)) return rc;
+        hipLaunchKernelGGL((k_dwm_fan_bwd<4>), gr, bl, lds, st, y, w, scale, g_x, P, F, (long long)planes);
+    } else {
+        if (int rc = dwm_raise_lds(who, seen1, (const void *)k_dwm_fan_bwd<1>, lds)) return rc;
+        hipLaunchKernelGGL((k_dwm_fan_bwd<1>), gr, bl, lds, st, y, w, scale, g_x, P, F, (long long)planes);
     }
     return check_launch(who);
 }

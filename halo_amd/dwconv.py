@@ -312,19 +312,43 @@ def multi_fallback_reason(x, blocks):
     return None
 
 
+def multi_forward(x, scale, shift, dil, ws):
+    """the forward launch over contiguous x: (w (n, C, 9) stacked, y (n, B, C, H, W)); counted as launches["multi_fwd"]"""
+    import ctypes
+    B, C, H, W = x.shape
+    n = len(ws)
+    w = torch.stack([wi.reshape(C, 9) for wi in ws])
+    y = torch.empty((n, B, C, H, W), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().halo_multi_dwconv3x3_affine_relu_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W,
+                                                               n, (ctypes.c_int64 * n)(*dil), _lib.stream_ptr(x.device)),
+               "halo_multi_dwconv3x3_affine_relu_fwd")
+    launches["multi_fwd"] += 1
+    return w, y
+
+
+def multi_weight_grads(gs, x, y, scale, dil, wanted):
+    """[g_w_i or None]: one halo_dwconv3x3_affine_relu_bwd_weight call per gradient that arrived (gs[i] contiguous float32, or None)
+    and is wanted"""
+    B, C, H, W = x.shape
+    L = _lib.lib()
+    st = _lib.stream_ptr(x.device)
+    gws = [None] * len(gs)
+    for i, g in enumerate(gs):
+        if g is None or not wanted[i]:
+            continue
+        nws = L.halo_dwconv_workspace_bytes(B, C, H, W, dil[i])
+        ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=x.device)
+        gws[i] = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
+        _lib.check(L.halo_dwconv3x3_affine_relu_bwd_weight(_lib.ptr(g), _lib.ptr(y[i]), _lib.ptr(x), _lib.ptr(scale[i]), _lib.ptr(gws[i]), B, C,
+                                                           H, W, dil[i], _lib.ptr(ws), ws.numel() * 8, st),
+                   "halo_dwconv3x3_affine_relu_bwd_weight")
+    return gws
+
+
 class _MultiDepthwiseBnReluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, scale, shift, dil, *ws):
-        import ctypes
-        B, C, H, W = x.shape
-        n = len(ws)
-        L = _lib.lib()
-        w = torch.stack([wi.reshape(C, 9) for wi in ws])
-        y = torch.empty((n, B, C, H, W), dtype=torch.float32, device=x.device)
-        _lib.check(L.halo_multi_dwconv3x3_affine_relu_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W, n,
-                                                          (ctypes.c_int64 * n)(*dil), _lib.stream_ptr(x.device)),
-                   "halo_multi_dwconv3x3_affine_relu_fwd")
-        launches["multi_fwd"] += 1
+        w, y = multi_forward(x, scale, shift, dil, ws)
         ctx.save_for_backward(x, y, w, scale)
         ctx.dil = dil
         ctx.set_materialize_grads(False)
@@ -337,28 +361,26 @@ class _MultiDepthwiseBnReluFn(torch.autograd.Function):
         x, y, w, scale = ctx.saved_tensors
         B, C, H, W = x.shape
         n, dil = len(gs), ctx.dil
-        L = _lib.lib()
-        st = _lib.stream_ptr(x.device)
         gs = [None if g is None else g.to(device=x.device, dtype=torch.float32).contiguous() for g in gs]
-        gx, gws = None, [None] * n
+        gx = None
         if all(g is None for g in gs):
             return (None,) * (4 + n)
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             ptrs = (ctypes.c_void_p * n)(*[None if g is None else g.data_ptr() for g in gs])
-            _lib.check(L.halo_multi_dwconv3x3_affine_relu_bwd_data(ptrs, _lib.ptr(y), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(gx), B, C, H, W, n,
-                                                                   (ctypes.c_int64 * n)(*dil), st), "halo_multi_dwconv3x3_affine_relu_bwd_data")
+            _lib.check(_lib.lib().halo_multi_dwconv3x3_affine_relu_bwd_data(ptrs, _lib.ptr(y), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(gx), B, C, H,
+                                                                            W, n, (ctypes.c_int64 * n)(*dil), _lib.stream_ptr(x.device)),
+                       "halo_multi_dwconv3x3_affine_relu_bwd_data")
             launches["multi_bwd"] += 1
-        for i, g in enumerate(gs):
-            if g is None or not ctx.needs_input_grad[4 + i]:
-                continue
-            nws = L.halo_dwconv_workspace_bytes(B, C, H, W, dil[i])
-            ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=x.device)
-            gws[i] = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
-            _lib.check(L.halo_dwconv3x3_affine_relu_bwd_weight(_lib.ptr(g), _lib.ptr(y[i]), _lib.ptr(x), _lib.ptr(scale[i]), _lib.ptr(gws[i]), B, C,
-                                                               H, W, dil[i], _lib.ptr(ws), ws.numel() * 8, st),
-                       "halo_dwconv3x3_affine_relu_bwd_weight")
-        return (gx, None, None, None) + tuple(gws)
+        return (gx, None, None, None) + tuple(multi_weight_grads(gs, x, y, scale, dil, ctx.needs_input_grad[4:]))
+
+
+def multi_operands(x, blocks):
+    """(x contiguous, scale (n, C), shift (n, C), the dilations, the contiguous weights): what the passes read of served blocks"""
+    pairs = [scale_shift(b[1]) for b in blocks]
+    scale, shift = torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
+    dil = tuple(int(_pair(b[0].dilation)[0]) for b in blocks)
+    return x.contiguous(), scale, shift, dil, [b[0].weight.contiguous() for b in blocks]
 
 
 def multi_depthwise_bn_relu(x, blocks):
@@ -372,10 +394,8 @@ def multi_depthwise_bn_relu(x, blocks):
         # called last block first: the engine runs the nodes made last first and adds the gradients of x as they arrive, so the
         # composition's g_x is ((gx_0 + gx_1) + gx_2) ... as well
         return tuple(reversed([depthwise_bn_relu(x, *b) for b in reversed(blocks)]))
-    pairs = [scale_shift(b[1]) for b in blocks]
-    scale, shift = torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
-    dil = tuple(int(_pair(b[0].dilation)[0]) for b in blocks)
-    return _MultiDepthwiseBnReluFn.apply(x.contiguous(), scale, shift, dil, *[b[0].weight.contiguous() for b in blocks])
+    x, scale, shift, dil, ws = multi_operands(x, blocks)
+    return _MultiDepthwiseBnReluFn.apply(x, scale, shift, dil, *ws)
 
 
 __all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift", "upsample_cat_depthwise_bn_relu", "upcat_fallback_reason",

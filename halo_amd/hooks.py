@@ -286,11 +286,10 @@ def use_fused_training_losses(learner_cls):
 # kept as `_unfused_forward`.  Neither install() nor the existing forward changes.
 
 def fused_v3plus_hyper_forward(self, x, size=None):
-    from .core.models.classifier import _tail_modules, aspp_pyramid, broadcast_or_resize, device_resize, folded_pooling, hyper_head_tail, v3plus_decoder
+    from .core.models.classifier import _tail_modules, pooled_aspp_pyramid, broadcast_or_resize, device_resize, folded_pooling, hyper_head_tail, v3plus_decoder
     from .hfr import weighted_normalize
     low, top = x["low"], x["out"]
-    pyramid = aspp_pyramid(self, top)
-    pooled = self.global_branch(top)
+    pyramid, pooled = pooled_aspp_pyramid(self, top)
     resize = device_resize(self)
     if folded_pooling(self, pooled):
         dec = v3plus_decoder(self, pyramid, low, resize, pooled=pooled)
@@ -441,6 +440,32 @@ def use_fused_aspp_depthwise(head_cls):
         raise TypeError("use_fused_aspp_depthwise: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
                         "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
     head_cls._halo_fused_aspp_depthwise = True
+    return head_cls
+
+
+# ---------------------------------------------------------------- the backbone output's five gradients added in one pass
+# Under use_fused_aspp_depthwise the dilated blocks' share of the backbone output's gradient is written once; the 1 x 1 branch's and
+# global_branch's shares are still joined to it by the engine: a full-size broadcast of one value per plane (MeanBackward1) and two
+# full-size adds.  `use_joined_aspp_gradients(head_cls)` marks a head class that carries one of the package's v3+ forwards; on a
+# class that use_fused_aspp_depthwise has marked as well, the first served run of dilated blocks runs as
+# halo_amd.fanout.fan_depthwise_bn_relu, whose backward adds the other readers' gradients where the run's sum leaves LDS
+# (core.models.classifier.pooled_aspp_pyramid: the conditions and the fallback).  A class attribute like use_fused_aspp_depthwise's:
+# opt-in, not bound by install(), composes with the other hooks in any order; parameters, module names and state_dict() are untouched.
+
+def use_joined_aspp_gradients(head_cls):
+    """Mark a v3+ head class (one that carries v3plus_hyper_forward, fused_v3plus_hyper_forward or v3plus_forward) so that the
+    gradient of the backbone's output is written once, by the pass that adds the dilated blocks' shares: the other parallel
+    branches' and global_branch's gradients join it there, the latter as one value per plane.  Acts on heads that
+    use_fused_aspp_depthwise marks too.  Returns the class.  Idempotent.  The marked head returns the bits of the same head under
+    use_fused_aspp_depthwise alone: both outputs and every parameter gradient.  Only the gradient of the backbone's output is
+    another association of the same five float32 terms t_i (the blocks' shares first, then the others in branch order), within
+    2 gamma_4 sum |t_i| of any other, the bound use_fused_aspp_depthwise documents."""
+    if not isinstance(head_cls, type):
+        raise TypeError("use_joined_aspp_gradients: expected a class, got %r" % (head_cls,))
+    if not any(_inherited(head_cls, "forward") is f for f in _package_forwards()[1:]):
+        raise TypeError("use_joined_aspp_gradients: %s does not carry one of halo_amd's v3+ forwards; bind one first with "
+                        "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
+    head_cls._halo_joined_aspp_gradients = True
     return head_cls
 
 

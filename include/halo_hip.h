@@ -446,6 +446,20 @@ int halo_multi_dwconv3x3_affine_relu_fwd(const float *x, const float *w, const f
 int halo_multi_dwconv3x3_affine_relu_bwd_data(const float *const *g, const float *y, const float *w, const float *scale, float *g_x,
                                               int64_t B, int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, void *stream);
 
+/* ---- the ASPP fan-out: the pyramid's backward with the gradients of x's other readers added in the same pass ----
+ *  The arguments of the multi bwd_data entry above, plus m extra addends, 0 <= m <= 4: e a HOST array of m device pointers (NULL: left
+ *  out), e_plane a HOST array of m flags -- 0: e[j] is (B, C, H, W) f32 dense NCHW; 1: e[j] is (B, C) f32, one value per plane that
+ *  enters as e[j][b C + c] at every pixel.
+ *    g_x = ((((gx_0 + gx_1) + gx_2) + e_0) + e_1) ...   float32 adds in list order, NULL g[i] and NULL e[j] left out: the bits of
+ *          the entry above followed by torch float32 adds of the addends.  m = 0 gives that entry's bits.
+ *  The addends join where the running sum leaves LDS, so the plane limit is halo_multi_dwconv_max_plane().  The 16-byte route also
+ *  needs every dense e[j] 16-byte aligned; otherwise one element per lane, the same bits.  At least one g[i] is not NULL.
+ *  HALO_E_ARG: the entry above's, m outside 0..4, e or e_plane NULL with m > 0; the other codes as above.  Every check comes
+ *  before any launch. */
+int halo_fan_dwconv3x3_affine_relu_bwd_data(const float *const *g, const float *y, const float *w, const float *scale, float *g_x,
+                                            int64_t B, int64_t C, int64_t H, int64_t W, int64_t n, const int64_t *d, int64_t m,
+                                            const float *const *e, const int32_t *e_plane, void *stream);
+
 /* ---- the front of the v3+ decoder: resize + concat + depthwise 3x3 conv + frozen norm + ReLU in one pass ----
  *  a (B, Ca, h, w), s (B, Cs, H, W) with H >= h, W >= w, y and g (B, Ca + Cs, H, W), g_up (B, Ca, H, W), g_s (B, Cs, H, W): f32 dense
  *  NCHW; w (Ca + Cs, 1, 3, 3), scale, shift (Ca + Cs) f32; dilation = padding = 1.
