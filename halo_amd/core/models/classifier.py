@@ -238,7 +238,8 @@ def v3plus_decoder(self, pyramid, low, resize, pooled=None, run=None):
     decoder[0] is a depthwise-separable block (the six DepthwiseSeparableConv2d attributes, an nn.ReLU depthwise_activate) inside
     the operator's envelope (upcat_fallback_reason); any other marked instance, and every unmarked class, runs the statements
     below.  A marked head returns what the same head returns under use_device_resize + use_fused_depthwise on that block, bit for
-    bit; that is not bit-equal to the stock F.interpolate / nn.Conv2d chain.
+    bit; that is not bit-equal to the stock F.interpolate / nn.Conv2d chain.  A head class that
+    halo_amd.hooks.use_joint_depthwise_backward marks as well passes joint_backward=True there: the same bits.
 
     All three tails hand the decoder's input to halo_amd.hooks.run_decoder: an unmarked head calls self.decoder (behind the fused
     front: decoder[0]'s pointwise half, then the remaining modules) as before; a block class marked by use_fused_pointwise_norm runs
@@ -266,7 +267,8 @@ def v3plus_decoder(self, pyramid, low, resize, pooled=None, run=None):
             top = bottleneck()
             short = self.shortcut(low)
             if upcat_fallback_reason(top, short, block.depthwise_conv, block.depthwise_bn) is None:
-                dec = upsample_cat_depthwise_bn_relu(top, short, block.depthwise_conv, block.depthwise_bn)
+                dec = upsample_cat_depthwise_bn_relu(top, short, block.depthwise_conv, block.depthwise_bn,
+                                                     joint_backward=getattr(type(self), "_halo_joint_depthwise_backward", False))
                 return run(self, dec, first_half_done=True)
             if resize is None:
                 fused = F.interpolate(top, size=low.shape[2:], mode="bilinear", align_corners=True)

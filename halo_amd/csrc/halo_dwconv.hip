@@ -415,6 +415,109 @@ __global__ void __launch_bounds__(DW_TPB) k_dw_upcat_wpart(const float *__restri
     dw_block_sum(acc, part);
 }
 
+// Both gradients from one walk: dw_walk_apply<DW_BWD> and dw_walk_wpart visit the same items in the same order, the first with a
+// window of gp, the second with a window of x and the centre group of gp's middle row.  A thread that keeps both windows runs the
+// statements of both per output row, in their order: g_x's nine terms (wk mirrored), then the float64 fmas for e ascending and k
+// ascending, then the store.  g, y and x are read once.  The parents' walks stay as they are (their registers are theirs).
+template <int GW, bool D1, typename SX>
+__device__ __forceinline__ void dw_walk_joint(SX &sx, const DwSrc<DW_BWD> &sg, const float (&wk)[9], float *__restrict__ op, const DwItem &it,
+                                              const DwGeom &G, double (&acc)[9])
+{
+    const int d = D1 ? 1 : G.d;
+    float xwin[3][3 * GW], gwin[3][3 * GW];
+    sx.template row<GW, D1>(xwin[0], it.i0 - d, it.c0, G.H, G.W, d);
+    sg.template row<GW, D1>(gwin[0], it.i0 - d, it.c0, G.H, G.W, d);
+    sx.template row<GW, D1>(xwin[1], it.i0, it.c0, G.H, G.W, d);
+    sg.template row<GW, D1>(gwin[1], it.i0, it.c0, G.H, G.W, d);
+    for (int i = it.i0; i < it.iend; i += d) {
+        sx.template row<GW, D1>(xwin[2], i + d, it.c0, G.H, G.W, d);
+        sg.template row<GW, D1>(gwin[2], i + d, it.c0, G.H, G.W, d);
+        float res[GW];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            float s = wk[0] * gwin[0][e];
+#pragma unroll
+            for (int k = 1; k < 9; ++k) s = __builtin_fmaf(wk[k], gwin[k / 3][(k % 3) * GW + e], s);
+            res[e] = s;
+        }
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            const double ge = (double)gwin[1][GW + e];       // gp at (i, c0 + e): what dw_walk_wpart loads through cols<GW, true>
+#pragma unroll
+            for (int k = 0; k < 9; ++k) acc[k] = __builtin_fma(ge, (double)xwin[k / 3][(k % 3) * GW + e], acc[k]);
+        }
+        if constexpr (GW == 4) {
+            dw_f4 v;
+            v.x = res[0], v.y = res[1], v.z = res[2], v.w = res[3];
+            *reinterpret_cast<dw_f4 *>(op + (size_t)i * G.W + it.c0) = v;
+        } else {
+            op[(size_t)i * G.W + it.c0] = res[0];
+        }
+#pragma unroll
+        for (int q = 0; q < 3 * GW; ++q) xwin[0][q] = xwin[1][q], xwin[1][q] = xwin[2][q], gwin[0][q] = gwin[1][q], gwin[1][q] = gwin[2][q];
+    }
+}
+
+// g_x = k_dw_apply<DW_BWD>'s, part = k_dw_wpart's rows.  Every thread reaches dw_block_sum: one without an item adds zeros.
+template <int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dw_joint(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ x,
+                                                     const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ g_x,
+                                                     double *__restrict__ part, DwGeom G)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const size_t po = (size_t)plane * G.H * G.W;
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    DwItem it;
+    if (dw_item<GW>(G, blk, it)) {
+        DwSrc<DW_FWD> sx;
+        sx.a = x + po, sx.y = nullptr, sx.scale = 0.0f;
+        DwSrc<DW_BWD> sg;
+        sg.a = g + po, sg.y = yv + po, sg.scale = scale[c];
+        float wk[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[k] = w[c * 9 + 8 - k];
+        dw_walk_joint<GW, D1>(sx, sg, wk, g_x + po, it, G, acc);
+    }
+    dw_block_sum(acc, part);
+}
+
+// The decoder front: k_dw_upcat_bwd over all Ca + Cs planes and k_dw_upcat_wpart in one walk.
+template <int GW>
+__global__ void __launch_bounds__(DW_TPB) k_dw_upcat_joint(const float *__restrict__ g, const float *__restrict__ yv, const float *__restrict__ a,
+                                                           const float *__restrict__ s, const float *__restrict__ w,
+                                                           const float *__restrict__ scale, float *__restrict__ g_up, float *__restrict__ g_s,
+                                                           double *__restrict__ part, DwGeom G, DwCat K)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const long long b = plane / G.C;
+    const size_t hw = (size_t)G.H * G.W, po = (size_t)plane * hw;
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    DwItem it;
+    if (dw_item<GW>(G, blk, it)) {
+        DwSrc<DW_BWD> sg;
+        sg.a = g + po, sg.y = yv + po, sg.scale = scale[c];
+        float wk[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[k] = w[c * 9 + 8 - k];
+        if (c < K.Ca) {
+            DwUpSrc<GW> sx;
+            sx.init(a + (size_t)(b * K.Ca + c) * K.h * K.w, K.h, K.w, K.sh, K.sw, it.c0, G.W);
+            dw_walk_joint<GW, GW == 4>(sx, sg, wk, g_up + (size_t)(b * K.Ca + c) * hw, it, G, acc);
+        } else {
+            DwSrc<DW_FWD> sx;
+            sx.a = s + (size_t)(b * K.Cs + (c - K.Ca)) * hw, sx.y = nullptr, sx.scale = 0.0f;
+            dw_walk_joint<GW, GW == 4>(sx, sg, wk, g_s + (size_t)(b * K.Cs + (c - K.Ca)) * hw, it, G, acc);
+        }
+    }
+    dw_block_sum(acc, part);
+}
+
 // g_w[c, k] = sum over images b, then blocks, in ascending order
 __global__ void __launch_bounds__(DW_TPB) k_dw_wsum(const double *__restrict__ part, float *__restrict__ gw, int B, int C, int bpp)
 {
@@ -870,6 +973,56 @@ extern "C" int halo_upcat_dwconv3x3_affine_relu_bwd_weight(const float *g, const
     const dim3 gr(grid), bl(DW_TPB);
     if (vec) hipLaunchKernelGGL((k_dw_upcat_wpart<4>), gr, bl, 0, st, g, y, a, s, scale, part, G, K);
     else hipLaunchKernelGGL((k_dw_upcat_wpart<1>), gr, bl, 0, st, g, y, a, s, scale, part, G, K);
+    hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
+    return check_launch(who);
+}
+
+extern "C" int halo_joint_dwconv3x3_affine_relu_bwd(const float *g, const float *y, const float *x, const float *w, const float *scale,
+                                                    float *g_x, float *g_w, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d,
+                                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "halo_joint_dwconv3x3_affine_relu_bwd";
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    if (!g || !y || !x || !w || !scale || !g_x || !g_w) return fail(HALO_E_ARG, "%s: null argument", who);
+    const size_t need = halo_dwconv_workspace_bytes(B, C, H, W, d);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 8) != 0)
+        return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (8-byte aligned)", who, workspace_bytes, need);
+    const bool vec = dw_vec(W, g, y, x, g_x);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    const dim3 gr(grid), bl(DW_TPB);
+    if (vec && d == 1) hipLaunchKernelGGL((k_dw_joint<4, true>), gr, bl, 0, st, g, y, x, w, scale, g_x, part, G);
+    else if (vec) hipLaunchKernelGGL((k_dw_joint<4, false>), gr, bl, 0, st, g, y, x, w, scale, g_x, part, G);
+    else hipLaunchKernelGGL((k_dw_joint<1, false>), gr, bl, 0, st, g, y, x, w, scale, g_x, part, G);
+    hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
+    return check_launch(who);
+}
+
+extern "C" int halo_joint_upcat_dwconv3x3_affine_relu_bwd(const float *g, const float *y, const float *a, const float *s, const float *w,
+                                                          const float *scale, float *g_up, float *g_s, float *g_w, int64_t B, int64_t Ca,
+                                                          int64_t Cs, int64_t h, int64_t w_in, int64_t H, int64_t W, void *workspace,
+                                                          size_t workspace_bytes, void *stream)
+{
+    const char *who = "halo_joint_upcat_dwconv3x3_affine_relu_bwd";
+    if (int rc = upcat_check(who, B, Ca, Cs, h, w_in, H, W)) return rc;
+    if (!g || !y || (Ca > 0 && (!a || !g_up)) || (Cs > 0 && (!s || !g_s)) || !w || !scale || !g_w) return fail(HALO_E_ARG, "%s: null argument", who);
+    const int64_t C = Ca + Cs;
+    const size_t need = halo_dwconv_workspace_bytes(B, C, H, W, 1);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 8) != 0)
+        return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (8-byte aligned)", who, workspace_bytes, need);
+    const bool vec = dw_vec(W, g, y, s, (const void *)((uintptr_t)g_up | (uintptr_t)g_s));
+    const DwGeom G = dw_geom(C, H, W, 1, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    const DwCat K = upcat_operands(Ca, Cs, h, w_in, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    const dim3 gr(grid), bl(DW_TPB);
+    if (vec) hipLaunchKernelGGL((k_dw_upcat_joint<4>), gr, bl, 0, st, g, y, a, s, w, scale, g_up, g_s, part, G, K);
+    else hipLaunchKernelGGL((k_dw_upcat_joint<1>), gr, bl, 0, st, g, y, a, s, w, scale, g_up, g_s, part, G, K);
     hipLaunchKernelGGL(k_dw_wsum, dim3((unsigned)cdiv(C * 9, DW_TPB)), bl, 0, st, (const double *)part, g_w, (int)B, (int)C, G.bpp);
     return check_launch(who);
 }

@@ -161,6 +161,15 @@ class _DepthwiseBnReluFn(torch.autograd.Function):
         st = _lib.stream_ptr(x.device)
         g = g.to(device=x.device, dtype=torch.float32).contiguous()
         gx = gw = None
+        if getattr(ctx, "joint", False) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
+            nws = L.halo_dwconv_workspace_bytes(B, C, H, W, d)
+            ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=x.device)
+            gx, gw = torch.empty_like(x), torch.empty_like(w)
+            _lib.check(L.halo_joint_dwconv3x3_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(x), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(gx),
+                                                              _lib.ptr(gw), B, C, H, W, d, _lib.ptr(ws), ws.numel() * 8, st),
+                       "halo_joint_dwconv3x3_affine_relu_bwd")
+            joint_launches["plain"] += 1
+            return gx, gw, None, None, None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             _lib.check(L.halo_dwconv3x3_affine_relu_bwd_data(_lib.ptr(g), _lib.ptr(y), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(gx), B, C, H, W, d,
@@ -174,13 +183,72 @@ class _DepthwiseBnReluFn(torch.autograd.Function):
         return gx, gw, None, None, None
 
 
-def depthwise_bn_relu(x, conv, bn, act=None):
+class _DepthwiseBnReluFnJoint(torch.autograd.Function):
+    """the same node with ctx.joint set: its backward takes the joint entry when both gradients are wanted.  A sibling, not a
+    subclass: it inherits nothing that a caller may have bound on _DepthwiseBnReluFn (tests wrap its `apply`)"""
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.joint = True
+        return _DepthwiseBnReluFn.forward(ctx, *args)
+
+    backward = staticmethod(_DepthwiseBnReluFn.backward)
+
+
+# ---------------------------------------------------------------- both gradients from one backward pass (opt-in)
+# With joint_backward=True a node whose differentiable inputs ALL need a gradient runs halo_joint_*_bwd: g, y and x are read once
+# for g_x and g_w, with the bits of the two calls it replaces (include/halo_hip.h).  Any other combination of needs runs those two
+# calls as before.  Counted per call of the joint entry:
+joint_launches = {"plain": 0, "upcat": 0}
+# A speed rule only (both sides return the same bits; the GPU tests switch it off with 0 everywhere).  Per route, the smallest
+# B * C * H * W at which the joint pass won against the two calls in both processes of profiles/r25_time_joint_depthwise.txt;
+# None: the route lost, or was not timed, and is not served.  Routes: "d1" and "dilated" are the 16-byte routes (W % 4 == 0) at
+# d = 1 and d > 1, "column" is the one-column route (any other W), "upcat" the decoder front (W % 4 == 0; C = Ca + Cs).
+#   d1       won at 1 and 2 x 512 x 160 x 320 (x1.39 / x1.41 and x1.24 / x1.22)
+#   dilated  lost at every shape timed (2048 x 80 x 160 and 2048 x 90 x 160, d = 6, 12, 18, B = 1 and 2: x0.83 to x0.99)
+#   column   not timed
+#   upcat    won at 1 and 2 x (512 + 48) x 160 x 320 and x 180 x 320 (x1.05 to x1.18)
+JOINT_MIN_ELEMENTS = {"d1": 1 * 512 * 160 * 320, "dilated": None, "column": None, "upcat": 1 * 560 * 160 * 320}
+
+
+def _joint_rule_reason(route, elements):
+    least = JOINT_MIN_ELEMENTS.get(route)
+    if least is None:
+        return "the joint backward's %r route is not served (a speed rule: it lost or was not timed)" % route
+    if elements < least:
+        return "%d elements, fewer than JOINT_MIN_ELEMENTS[%r] = %d (a speed rule: nothing smaller won)" % (elements, route, least)
+    return None
+
+
+def joint_fallback_reason(x, conv, bn):
+    """why depthwise_bn_relu(x, conv, bn, joint_backward=True) runs its backward as two calls, or the torch statements (None: a
+    backward that wants both gradients runs the joint entry).  The block's own fallback_reason, or the speed rule.  Reads no
+    device memory."""
+    why = fallback_reason(x, conv, bn)
+    if why is not None:
+        return why
+    B, C, H, W = x.shape
+    d = int(_pair(conv.dilation)[0])
+    return _joint_rule_reason("column" if W % 4 else ("d1" if d == 1 else "dilated"), B * C * H * W)
+
+
+def upcat_joint_fallback_reason(a, s, conv, bn):
+    """joint_fallback_reason for upsample_cat_depthwise_bn_relu(a, s, conv, bn, joint_backward=True)"""
+    why = upcat_fallback_reason(a, s, conv, bn)
+    if why is not None:
+        return why
+    B, Cs, H, W = s.shape
+    return _joint_rule_reason("column" if W % 4 else "upcat", B * (a.shape[1] + Cs) * H * W)
+
+
+def depthwise_bn_relu(x, conv, bn, act=None, joint_backward=False):
     """relu(bn(conv(x))) of a depthwise 3x3 conv and a frozen / eval-mode norm, x (B, C, H, W).  Differentiable w.r.t. x and
-    conv.weight.  Outside the served envelope (fallback_reason) it returns torch_statement(x, conv, bn, act)."""
+    conv.weight.  Outside the served envelope (fallback_reason) it returns torch_statement(x, conv, bn, act).
+    joint_backward=True: a backward that wants both gradients computes them in one pass (joint_fallback_reason; the same bits)."""
     if fallback_reason(x, conv, bn) is not None:
         return torch_statement(x, conv, bn, act)
     scale, shift = scale_shift(bn)
-    return _DepthwiseBnReluFn.apply(x.contiguous(), conv.weight.contiguous(), scale, shift, int(_pair(conv.dilation)[0]))
+    fn = _DepthwiseBnReluFnJoint if joint_backward and joint_fallback_reason(x, conv, bn) is None else _DepthwiseBnReluFn
+    return fn.apply(x.contiguous(), conv.weight.contiguous(), scale, shift, int(_pair(conv.dilation)[0]))
 
 
 def upcat_fallback_reason(a, s, conv, bn):
@@ -234,6 +302,19 @@ class _UpCatDepthwiseBnReluFn(torch.autograd.Function):
         g = g.to(device=s.device, dtype=torch.float32).contiguous()
         need_a, need_s, need_w = ctx.needs_input_grad[:3]
         ga = gs = gw = None
+        if getattr(ctx, "joint", False) and need_a and need_s and need_w:
+            nws = L.halo_dwconv_workspace_bytes(B, Ca + Cs, H, W, 1)
+            ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=s.device)
+            gup = torch.empty((B, Ca, H, W), dtype=torch.float32, device=s.device)
+            gs, gw, ga = torch.empty_like(s), torch.empty_like(w), torch.empty_like(a)
+            _lib.check(L.halo_joint_upcat_dwconv3x3_affine_relu_bwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(a), _lib.ptr(s), _lib.ptr(w),
+                                                                    _lib.ptr(scale), _lib.ptr(gup), _lib.ptr(gs), _lib.ptr(gw), B, Ca, Cs, h,
+                                                                    wi, H, W, _lib.ptr(ws), ws.numel() * 8, st),
+                       "halo_joint_upcat_dwconv3x3_affine_relu_bwd")
+            joint_launches["upcat"] += 1
+            _lib.check(L.halo_bilinear_upsample_bwd(_lib.ptr(gup), _lib.ptr(ga), _lib.dtype_code(gup), B * Ca, h, wi, H, W, st),
+                       "halo_bilinear_upsample_bwd")
+            return ga, gs, gw, None, None
         if need_a or need_s:
             gup = torch.empty((B, Ca, H, W), dtype=torch.float32, device=s.device) if need_a else None
             gs = torch.empty_like(s) if need_s else None
@@ -255,18 +336,31 @@ class _UpCatDepthwiseBnReluFn(torch.autograd.Function):
         return ga, gs, gw, None, None
 
 
-def upsample_cat_depthwise_bn_relu(a, s, conv, bn, act=None):
+class _UpCatDepthwiseBnReluFnJoint(torch.autograd.Function):
+    """the same node with ctx.joint set: its backward takes the joint entry when all three gradients are wanted (a sibling, as above)"""
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.joint = True
+        return _UpCatDepthwiseBnReluFn.forward(ctx, *args)
+
+    backward = staticmethod(_UpCatDepthwiseBnReluFn.backward)
+
+
+def upsample_cat_depthwise_bn_relu(a, s, conv, bn, act=None, joint_backward=False):
     """relu(bn(conv(cat([resize(a, s.shape[2:]), s], 1)))) for a (B, Ca, h, w), s (B, Cs, H, W), a depthwise 3x3 conv of Ca + Cs
     channels at dilation 1 and a frozen / eval-mode norm: y (B, Ca + Cs, H, W), the resize bilinear with align_corners=True.
     Neither the resized nor the concatenated tensor is stored, forward or backward.  Differentiable once w.r.t. a, s and
     conv.weight.  The bits are those of depthwise_bn_relu(torch.cat([bilinear_resize(a, (H, W)), s], 1), conv, bn): not those of
     the stock F.interpolate / nn.Conv2d chain.  Outside the served envelope (upcat_fallback_reason) it returns
-    depthwise_bn_relu(torch.cat([resize_or_interpolate(a, (H, W)), s], 1), conv, bn, act), which has its own fallbacks."""
+    depthwise_bn_relu(torch.cat([resize_or_interpolate(a, (H, W)), s], 1), conv, bn, act), which has its own fallbacks.
+    joint_backward=True: a backward that wants the gradients of a, s and conv.weight computes them in one pass
+    (upcat_joint_fallback_reason; the same bits); the composition outside the envelope gets the keyword as well."""
     if upcat_fallback_reason(a, s, conv, bn) is not None:
         from .resize import resize_or_interpolate
-        return depthwise_bn_relu(torch.cat([resize_or_interpolate(a, tuple(s.shape[2:])), s], 1), conv, bn, act)
+        return depthwise_bn_relu(torch.cat([resize_or_interpolate(a, tuple(s.shape[2:])), s], 1), conv, bn, act, joint_backward)
     scale, shift = scale_shift(bn)
-    return _UpCatDepthwiseBnReluFn.apply(a.contiguous(), s.contiguous(), conv.weight.contiguous(), scale, shift)
+    fn = _UpCatDepthwiseBnReluFnJoint if joint_backward and upcat_joint_fallback_reason(a, s, conv, bn) is None else _UpCatDepthwiseBnReluFn
+    return fn.apply(a.contiguous(), s.contiguous(), conv.weight.contiguous(), scale, shift)
 
 
 # ---------------------------------------------------------------- the ASPP pyramid: N dilations over one input
@@ -399,4 +493,5 @@ def multi_depthwise_bn_relu(x, blocks):
 
 
 __all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift", "upsample_cat_depthwise_bn_relu", "upcat_fallback_reason",
-           "multi_depthwise_bn_relu", "multi_fallback_reason", "multi_max_plane", "launches"]
+           "multi_depthwise_bn_relu", "multi_fallback_reason", "multi_max_plane", "launches", "joint_fallback_reason",
+           "upcat_joint_fallback_reason", "joint_launches", "JOINT_MIN_ELEMENTS"]

@@ -362,7 +362,8 @@ _DWSEP_ATTRS = ("depthwise_conv", "depthwise_bn", "depthwise_activate", "pointwi
 def fused_dwsep_forward(self, x):
     from .dwconv import depthwise_bn_relu, torch_statement
     if type(self.depthwise_activate) is torch.nn.ReLU:
-        x = depthwise_bn_relu(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate)
+        x = depthwise_bn_relu(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate,
+                              joint_backward=getattr(type(self), "_halo_joint_depthwise_backward", False))
     else:
         x = torch_statement(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate)
     return pointwise_tail(self, x)
@@ -416,6 +417,30 @@ def use_fused_decoder_front(head_cls):
                         "halo_amd.install(), use_fused_feature_reweighting or use_v3plus_forward" % head_cls.__name__)
     head_cls._halo_fused_decoder_front = True
     return head_cls
+
+
+# ---------------------------------------------------------------- a separable block's two gradients from one backward pass
+# The backward of a block's depthwise half is two passes over g, y and x: one for g_x, one for g_w.  `use_joint_depthwise_backward(cls)`
+# marks a class so that a backward that wants every gradient of the node runs halo_joint_*_bwd instead (halo_amd.dwconv: the
+# keyword joint_backward, the envelope and the speed rule JOINT_MIN_ELEMENTS, under which a route that did not win its timing is
+# not served).  A class attribute like use_fused_decoder_front's: opt-in, not bound by install(), composes with the other hooks in any
+# order; parameters, module names and state_dict() are untouched.
+
+def use_joint_depthwise_backward(cls):
+    """Mark a depthwise-separable block class (see use_fused_depthwise: fused_dwsep_forward reads the mark and passes it to
+    depthwise_bn_relu as joint_backward) or a v3+ head class that carries v3plus_hyper_forward, fused_v3plus_hyper_forward or
+    v3plus_forward (v3plus_decoder reads the mark for the front under use_fused_decoder_front).  Returns the class.  Idempotent.
+    The mark alone binds no forward: a block class acts under use_fused_depthwise, a head class under use_fused_decoder_front.  A
+    marked class returns the bits of the unmarked one: outputs, every input gradient and every parameter gradient.  Under
+    use_fused_aspp_depthwise the three pyramid blocks run the pyramid pass and its weight-gradient calls as before; the mark then
+    acts on the decoder blocks only."""
+    if not isinstance(cls, type):
+        raise TypeError("use_joint_depthwise_backward: expected a class, got %r" % (cls,))
+    if not _is_dwsep_class(cls) and not any(_inherited(cls, "forward") is f for f in _package_forwards()[1:]):
+        raise TypeError("use_joint_depthwise_backward: %s is neither a depthwise-separable block class (instances with %s) nor a head "
+                        "class that carries one of halo_amd's v3+ forwards" % (cls.__name__, ", ".join(_DWSEP_ATTRS)))
+    cls._halo_joint_depthwise_backward = True
+    return cls
 
 
 # ---------------------------------------------------------------- the ASPP pyramid's dilated depthwise halves in one pass each way
@@ -839,7 +864,8 @@ def depthwise_half(block, x):
     use_fused_depthwise, the three stock statements otherwise"""
     if _inherited(type(block), "forward") is fused_dwsep_forward and type(block.depthwise_activate) is torch.nn.ReLU:
         from .dwconv import depthwise_bn_relu
-        return depthwise_bn_relu(x, block.depthwise_conv, block.depthwise_bn, block.depthwise_activate)
+        return depthwise_bn_relu(x, block.depthwise_conv, block.depthwise_bn, block.depthwise_activate,
+                                 joint_backward=getattr(type(block), "_halo_joint_depthwise_backward", False))
     return block.depthwise_activate(block.depthwise_bn(block.depthwise_conv(x)))
 
 

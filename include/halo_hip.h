@@ -480,7 +480,27 @@ int halo_upcat_dwconv3x3_affine_relu_bwd_weight(const float *g, const float *y, 
                                                 float *g_w, int64_t B, int64_t Ca, int64_t Cs, int64_t h, int64_t w_in, int64_t H, int64_t W,
                                                 void *workspace, size_t workspace_bytes, void *stream);
 
-/* ---- frozen norm + residual add + ReLU of a ResNet block (core/models/resnet.py:53-69, 92-112; core/models/layers.py) ----
+/* ---- both gradients of a depthwise block from one pass: g, y and x are read once, g_x is written once ----
+ *  The operands of the bwd_data and bwd_weight calls above (plain, and the decoder front's); a thread keeps the window of gp and the
+ *  window of x and runs the statements of both calls per output row, in their order.  All outputs are required (the front's g_up
+ *  when Ca > 0, g_s when Cs > 0).  The workspace is bwd_weight's: halo_dwconv_workspace_bytes(B, C, H, W, d), for the front
+ *  (B, Ca + Cs, H, W, 1).  16-byte loads and stores only when W % 4 == 0 and ALL of g, y, x, g_x (the front: g, y, s, g_up, g_s)
+ *  are 16-byte aligned; one column per thread otherwise.
+ *    g_x (g_up | g_s) carries the bits of ..._bwd_data on either route: its sums do not depend on the route.
+ *    g_w carries the bits of ..._bwd_weight whenever that call takes the same route on g, y, x (the front: g, y, s).  In the one
+ *        remaining case -- those aligned, W % 4 == 0, and only g_x (g_up, g_s) misaligned -- g_w equals ..._bwd_weight on the
+ *        one-column route (what it returns for the same values at a misaligned x).
+ *  Checks in the parents' order, before any launch: the shape (HALO_E_ARG / HALO_E_UNSUPPORTED as above), a missing pointer
+ *  (HALO_E_ARG), the workspace (HALO_E_WORKSPACE: short, NULL or not 8-byte aligned).  No atomics: repeated calls give identical bits. */
+int halo_joint_dwconv3x3_affine_relu_bwd(const float *g, const float *y, const float *x, const float *w, const float *scale, float *g_x,
+                                         float *g_w, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+int halo_joint_upcat_dwconv3x3_affine_relu_bwd(const float *g, const float *y, const float *a, const float *s, const float *w,
+                                               const float *scale, float *g_up, float *g_s, float *g_w, int64_t B, int64_t Ca, int64_t Cs,
+                                               int64_t h, int64_t w_in, int64_t H, int64_t W, void *workspace, size_t workspace_bytes,
+                                               void *stream);
+
+/* ---- frozen norm + residual add + ReLU of a ResNet block(core/models/resnet.py:53-69, 92-112; core/models/layers.py) ----
  *  x, r, y, g, g_x, g_r (B, C, HW) f32 dense NCHW planes; scale, shift, r_scale, r_shift (C) f32.
  *    pre = fl(fl(x scale[c]) + shift[c]);  id = r  or  fl(fl(r r_scale[c]) + r_shift[c]);  y = relu(pre)  or  relu(fl(pre + id))
  *    gp = y <= 0 ? 0 : g;  g_x = fl(gp scale[c]);  g_r = gp  or  fl(gp r_scale[c])
