@@ -33,6 +33,15 @@ constexpr int TPB = 256;
 #ifndef HALO_FEAT_UNROLL
 #define HALO_FEAT_UNROLL 8
 #endif
+#ifndef HALO_FEAT_STORE           // how the 16-byte radius store leaves the chip (feat_store): 1 plain, 2 nt, 3 sc1, 4 sc0 sc1
+#define HALO_FEAT_STORE 2
+#endif
+#ifndef HALO_FEAT_ENT_STORE       // the fused entropy's 8-byte store: 0 plain, 1 under HALO_FEAT_STORE's policy
+#define HALO_FEAT_ENT_STORE 1
+#endif
+#ifndef HALO_FEAT_LOGIT_NT        // the fused entropy's 8-byte class-plane loads: 0 plain, 1 nt (read once, like the feature planes)
+#define HALO_FEAT_LOGIT_NT 1
+#endif
 constexpr int FTPB = HALO_FTPB;   // k_feat_reduce: 128-thread blocks stream ~3 % faster than 256 (tools/feat_microbench.hip)
 
 // ---------------------------------------------------------------- reductions
@@ -301,6 +310,7 @@ __device__ __forceinline__ float fma_t(float a, float b, float c) { return __bui
 template <typename T, int VEC> struct VecLoad;
 typedef double d2_t __attribute__((ext_vector_type(2)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
+typedef float f2_t __attribute__((ext_vector_type(2)));
 template <> struct VecLoad<double, 2> {
     static __device__ __forceinline__ void ld(const double *p, double (&v)[2])
     {
@@ -318,6 +328,36 @@ template <> struct VecLoad<float, 4> {
 template <typename T> struct VecLoad<T, 1> {
     static __device__ __forceinline__ void ld(const T *p, T (&v)[1]) { v[0] = *p; }
 };
+
+// k_feat_reduce's result stores.  A plain store retires into the XCD's write-back L2 and leaves it whenever the read stream
+// displaces its line; the walk then runs 3.5 % (fast stretches of HBM) to 10 % (slow ones) below a walk that stores nothing.
+// With nt, sc1 or sc0 sc1 on the store the walk recovers 45 % / 60 % of that, the three alike, 8 bytes per lane as well as
+// 16 (tools/probe_walk_stores.py, profiles/r26_walk_store_modes.txt).  SM: 1 plain, 2 nt, 3 sc1, 4 sc0 sc1 -- 2-4 as a
+// buffer store (the policy is its cache-bits operand; the compiler counts and schedules it like any store).  `chunk` is the
+// block's part of the map and block-uniform (the descriptor lives in SGPRs), `chunk_bytes` what of it lies inside the map
+// (the hardware drops a store past it), `off` this lane's byte offset in it.
+typedef unsigned int su4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int su2_t __attribute__((ext_vector_type(2)));
+template <int SM, typename V>
+__device__ __forceinline__ void feat_store(void *chunk, unsigned chunk_bytes, unsigned off, const V &v)
+{
+    static_assert(SM >= 1 && SM <= 4 && (sizeof(V) == 16 || sizeof(V) == 8), "feat_store: store mode 1..4, 8 or 16 bytes per lane");
+    if constexpr (SM == 1) {
+        *reinterpret_cast<V *>(static_cast<char *>(chunk) + off) = v;
+    } else {
+        constexpr int AUX = SM == 2 ? 2 : SM == 3 ? 16 : 17;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(chunk, 0, (int)chunk_bytes, 0x00020000);
+        if constexpr (sizeof(V) == 16) {
+            su4_t w;
+            __builtin_memcpy(&w, &v, 16);
+            __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)off, 0, AUX);
+        } else {
+            su2_t w;
+            __builtin_memcpy(&w, &v, 8);
+            __builtin_amdgcn_raw_buffer_store_b64(w, rs, (int)off, 0, AUX);
+        }
+    }
+}
 
 // MODE 0: poincare_distance_origin (pur 'radius' / 'hyper'), MODE 1: decoder_out.norm(dim=1) ('euc_norm')
 // FO > 0: also compute the per-pixel entropy of the FO-class logits of the same pixels (what
@@ -354,6 +394,7 @@ __global__ void __launch_bounds__(FTPB) __attribute__((amdgpu_waves_per_eu(1, HA
     const unsigned lane0 = threadIdx.x * VEC;
     const long long i0 = blk0 + lane0;
     const bool live = i0 < hw;
+    const unsigned chunk_px = (unsigned)(hw - blk0 < FTPB * VEC ? hw - blk0 : FTPB * VEC);     // the chunk's pixels inside the map
 #if HALO_LOGF_LDS
     __shared__ double s_ltab[FO > 0 ? 128 : 1][2];
     if constexpr (FO > 0) stage_logf_table<FTPB>(s_ltab);
@@ -386,7 +427,11 @@ __global__ void __launch_bounds__(FTPB) __attribute__((amdgpu_waves_per_eu(1, HA
 #pragma unroll
                     for (int c2 = 0; c2 < FO; ++c2, plane += hw) {
                         if constexpr (NP == 2) {
+#if HALO_FEAT_LOGIT_NT
+                            const f2_t q = __builtin_nontemporal_load(reinterpret_cast<const f2_t *>(plane + off));
+#else
                             const float2 q = *reinterpret_cast<const float2 *>(plane + off);
+#endif
                             lv[0][c2] = q.x; lv[1][c2] = q.y;
                         } else {
                             lv[0][c2] = plane[off];
@@ -403,7 +448,7 @@ __global__ void __launch_bounds__(FTPB) __attribute__((amdgpu_waves_per_eu(1, HA
 #pragma unroll 1
                         for (int j = 0; j < NP; ++j) px_general(lp + off + j, FO, hw, 0, unc_type, HALO_PUR_NONE, 0, e[j], pr[j]);
                     }
-                    if constexpr (NP == 2) *reinterpret_cast<float2 *>(eb + off) = make_float2(e[0], e[1]);
+                    if constexpr (NP == 2) feat_store<(HALO_FEAT_ENT_STORE ? HALO_FEAT_STORE : 1)>(eb, chunk_px * 4u, off * 4u, make_float2(e[0], e[1]));
                     else eb[off] = e[0];
                 }
                 __builtin_amdgcn_sched_barrier(0);      // keep the next part's loads (and registers) out of this one
@@ -443,10 +488,10 @@ __global__ void __launch_bounds__(FTPB) __attribute__((amdgpu_waves_per_eu(1, HA
             else if constexpr (sizeof(T) == 8) r[j] = __builtin_sqrt(acc[j]);
             else r[j] = __builtin_sqrtf(acc[j]);
         }
-        T *op = (out + (size_t)b * hw + blk0) + lane0;
-        if constexpr (VEC == 2) *reinterpret_cast<double2 *>(op) = make_double2(r[0], r[1]);
-        else if constexpr (VEC == 4) *reinterpret_cast<float4 *>(op) = make_float4(r[0], r[1], r[2], r[3]);
-        else op[0] = r[0];
+        T *ob = out + (size_t)b * hw + blk0;
+        if constexpr (VEC == 2) feat_store<HALO_FEAT_STORE>(ob, chunk_px * 8u, lane0 * 8u, make_double2(r[0], r[1]));
+        else if constexpr (VEC == 4) feat_store<HALO_FEAT_STORE>(ob, chunk_px * 4u, lane0 * 4u, make_float4(r[0], r[1], r[2], r[3]));
+        else ob[lane0] = r[0];                            // the one-pixel route keeps the plain store
         mn = mx = (double)r[0];
 #pragma unroll
         for (int j = 1; j < VEC; ++j) { mn = nan_min(mn, (double)r[j]); mx = nan_max(mx, (double)r[j]); }

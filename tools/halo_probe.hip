@@ -63,9 +63,89 @@ k_walk_probe(const pd2_t *__restrict__ x, size_t plane16, int planes, unsigned x
     out[(size_t)blockIdx.y * plane16 + (size_t)bx * 128 + threadIdx.x] = r;
 }
 
+// k_walk_probe with the result store as a template parameter (tools/probe_walk_stores.py): the same walk, the same 16 bytes per
+// lane, another way for them to leave the chip.  SM 0: no store (the sums kept alive by a store that is practically never
+// taken), 1: the plain store of k_walk_probe, 2: nt, 3: sc1, 4: sc0 sc1 (write-through), 5: sc0 sc1 at 8 bytes per lane from
+// every lane, twice (the fused entropy store's shape: a wave writes two 512-byte runs).  2-5 are buffer stores with the
+// policy in the instruction's cache bits (aux: nt = 2, sc1 = 16, sc0 = 1); the descriptor covers exactly the chunk's 2 KiB.
+// Chunk o's result lands `skew16` 16-byte units further into the group's result plane, modulo the plane (whole chunks).
+typedef unsigned int pu4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int pu2_t __attribute__((ext_vector_type(2)));
+template <int SM>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 4)))
+k_walk_probe_ex(const pd2_t *__restrict__ x, size_t plane16, int planes, unsigned xcd_g, pd2_t *__restrict__ out, size_t skew16)
+{
+    unsigned bx = blockIdx.x;
+    const unsigned xj = blockIdx.x >> 3;
+    if (xcd_g != 0 && blockIdx.x < (gridDim.x / (8 * xcd_g)) * (8 * xcd_g)) bx = (xj / xcd_g) * 8 * xcd_g + (blockIdx.x & 7) * xcd_g + xj % xcd_g;
+    const pd2_t *p = x + (size_t)blockIdx.y * planes * plane16 + (size_t)bx * 128 + threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+    int c = 0;
+    for (; c + 8 <= planes; c += 8) {
+        pd2_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u, p += plane16) v[u] = __builtin_nontemporal_load(p);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { a0 = __builtin_fma(v[u].x, v[u].x, a0); a1 = __builtin_fma(v[u].y, v[u].y, a1); }
+    }
+    for (; c < planes; ++c, p += plane16) { const pd2_t v = __builtin_nontemporal_load(p); a0 = __builtin_fma(v.x, v.x, a0); a1 = __builtin_fma(v.y, v.y, a1); }
+    pd2_t r; r.x = a0; r.y = a1;
+    size_t dst16 = (size_t)bx * 128 + skew16;
+    if (dst16 >= plane16) dst16 -= plane16;                       // skew16 < plane16, both whole chunks (checked by the host)
+    pd2_t *chunk = out + (size_t)blockIdx.y * plane16 + dst16;    // block-uniform
+    if constexpr (SM == 0) {
+        if (a0 == -1.0 && a1 == -2.0) chunk[threadIdx.x] = r;     // sums of squares: never taken
+    } else if constexpr (SM == 1) {
+        chunk[threadIdx.x] = r;
+    } else {
+        constexpr int AUX = SM == 2 ? 2 : SM == 3 ? 16 : 17;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(chunk, 0, 2048, 0x00020000);
+        pu4_t w;
+        __builtin_memcpy(&w, &r, 16);
+        if constexpr (SM == 5) {
+            pu2_t lo, hi;
+            lo.x = w.x; lo.y = w.y; hi.x = w.z; hi.y = w.w;
+            __builtin_amdgcn_raw_buffer_store_b64(lo, rs, threadIdx.x * 8, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(hi, rs, 1024 + threadIdx.x * 8, 0, AUX);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b128(w, rs, threadIdx.x * 16, 0, AUX);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" const char *halo_probe_last_error(void) { return g_err; }
+
+extern "C" int halo_hbm_walk_probe_ex(const void *buf, size_t bytes, size_t plane_bytes, int planes, void *out, int store_mode,
+                                      size_t out_skew_bytes, void *stream)
+{
+    if (!buf || !out || ((uintptr_t)buf & 15) || ((uintptr_t)out & 15) || planes <= 0 || plane_bytes == 0 || (plane_bytes & 2047))
+        return fail(PROBE_E_ARG, "halo_hbm_walk_probe_ex: 16-byte aligned buffers, planes > 0 and plane_bytes a multiple of 2048 required");
+    if (store_mode < 0 || store_mode > 5) return fail(PROBE_E_ARG, "halo_hbm_walk_probe_ex: store_mode 0..5");
+    if ((out_skew_bytes & 2047) || out_skew_bytes >= plane_bytes)
+        return fail(PROBE_E_ARG, "halo_hbm_walk_probe_ex: out_skew_bytes must be a multiple of 2048 below plane_bytes");
+    const size_t group = plane_bytes * (size_t)planes;
+    if (bytes < group || bytes % group) return fail(PROBE_E_ARG, "halo_hbm_walk_probe_ex: bytes must be a whole number of groups of planes * plane_bytes");
+    const size_t groups = bytes / group, chunks = plane_bytes / 2048;
+    if (groups > 65535 || chunks > 0x7fffffffull) return fail(PROBE_E_ARG, "halo_hbm_walk_probe_ex: too many groups / chunks");
+    unsigned xcd_g = 256;
+    while (xcd_g > 1 && 8 * xcd_g > chunks) xcd_g >>= 1;
+    if (8 * xcd_g > chunks) xcd_g = 0;
+    const dim3 grid((unsigned)chunks, (unsigned)groups), block(128);
+#define WALK_EX(SM_) hipLaunchKernelGGL((k_walk_probe_ex<SM_>), grid, block, 0, (hipStream_t)stream, (const pd2_t *)buf, plane_bytes / 16, planes, \
+                                        xcd_g, (pd2_t *)out, out_skew_bytes / 16)
+    switch (store_mode) {
+    case 0: WALK_EX(0); break;
+    case 1: WALK_EX(1); break;
+    case 2: WALK_EX(2); break;
+    case 3: WALK_EX(3); break;
+    case 4: WALK_EX(4); break;
+    default: WALK_EX(5); break;
+    }
+#undef WALK_EX
+    return check_launch("halo_hbm_walk_probe_ex");
+}
 
 extern "C" int halo_hbm_walk_probe(const void *buf, size_t bytes, size_t plane_bytes, int planes, void *out, void *stream)
 {

@@ -47,6 +47,8 @@ def lib():
         h.halo_hbm_read_probe.argtypes = [vp, sz, vp, C.c_int, vp]
         h.halo_hbm_walk_probe.restype = C.c_int
         h.halo_hbm_walk_probe.argtypes = [vp, sz, sz, C.c_int, vp, vp]
+        h.halo_hbm_walk_probe_ex.restype = C.c_int
+        h.halo_hbm_walk_probe_ex.argtypes = [vp, sz, sz, C.c_int, vp, C.c_int, sz, vp]
         h.halo_pool_alloc.restype = vp
         h.halo_pool_alloc.argtypes = [sz, C.c_int, vp]
         h.halo_pool_free.restype = None
@@ -80,6 +82,17 @@ def read_probe(t, nbytes=None, sink=None, offset=0):
 def walk_probe(t, nbytes, plane_bytes, planes, out, offset=0):
     check(lib().halo_hbm_walk_probe(t.data_ptr() + offset, int(nbytes), int(plane_bytes), int(planes), out.data_ptr(), _stream(t.device)),
           "halo_hbm_walk_probe")
+
+
+STORE_MODES = ("none", "plain", "nt", "sc1", "sc0 sc1", "sc0 sc1 8B")
+
+
+def walk_probe_ex(t, nbytes, plane_bytes, planes, out, store_mode, out_skew_bytes=0, offset=0):
+    """walk_probe with the 16-byte result store issued as STORE_MODES[store_mode], chunk o's result `out_skew_bytes` further into
+    its result plane (modulo the plane); `out` holds one plane per group of planes."""
+    assert out.numel() * out.element_size() >= int(nbytes) // int(planes)
+    check(lib().halo_hbm_walk_probe_ex(t.data_ptr() + offset, int(nbytes), int(plane_bytes), int(planes), out.data_ptr(), int(store_mode),
+                                       int(out_skew_bytes), _stream(t.device)), "halo_hbm_walk_probe_ex")
 
 
 def flat_read_gbps(t, reps=5):
