@@ -20,6 +20,8 @@ LOSS_CE, LOSS_NL = 1, 2                                             # HALO_LOSS_
 SWEEP_REASONS = ("done", "bad_values", "bin_overflow", "survivors", "exhausted", "not_run")      # HALO_SWEEP_*
 PAD = {"zeros": 0, "reflect": 1, "replicate": 2, "circular": 3}     # HALO_PAD_*: nn.Conv2d's padding_mode values
 FLAG_NORMALIZE = 1
+WINDOW = {"box": 0, "hist": 1}                                      # HALO_WINDOW_*: the two window passes of the scorer
+WINDOW_ROUTES = ("generic", "tile3", "tiled")                       # halo_window_route's return values
 
 
 def score_flags(normalize, padding_mode="zeros"):
@@ -69,6 +71,7 @@ SIGNATURES = {
     "halo_score": (_int, [C.POINTER(ScoreArgs), _vp]),
     "halo_region_uncertainty": (_int, [_vp, _i64, _int, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _sz, _vp]),
     "halo_region_impurity": (_int, [_vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _int, _vp]),
+    "halo_window_route": (_int, [_int, _int, _int, _i64, _i64, _i64]),
     "halo_quantize_radius": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _vp, _vp, _sz, _vp]),
     "halo_loss_workspace_bytes": (_sz, [_i64]),
     "halo_negative_learning_fwd": (_int, [_vp, _i64, _dbl, _vp, _vp, _sz, _vp]),

@@ -77,6 +77,22 @@ def new_score_range(B, dev):
     return torch.empty((int(B), int(n)), dtype=torch.uint8, device=dev)
 
 
+def window_route(what, size, padding_mode="zeros", bins=19, shape=None):
+    """Which kernels serve a size x size window pass: what = 'box' (the uncertainty's box sum) or 'hist' (the purity window's
+    class histogram over `bins` classes) on maps of `shape` = (H, W) (None: 1024 x 2048).  Returns 'generic' (one thread per
+    pixel, every tap from device memory), 'tile3' (the 3 x 3 zero-padding tile kernels) or 'tiled' (the LDS-tiled wide-window
+    kernels: odd sizes 5 to 33, every padding mode, at most 32 bins).  The library's launchers branch on the same function
+    (halo_window_route); every route computes the same bits.  An even size is the library's argument error."""
+    if padding_mode not in _lib.PAD:
+        raise ValueError("padding_mode must be one of %s, got %r" % (sorted(_lib.PAD), padding_mode))
+    H, W = (1024, 2048) if shape is None else (int(shape[-2]), int(shape[-1]))
+    L = _lib.lib()
+    rc = L.halo_window_route(_lib.WINDOW[what] if what in _lib.WINDOW else int(what), int(size), _lib.PAD[padding_mode], int(bins), H, W)
+    if rc < 0:
+        _lib.check(rc, "halo_window_route")
+    return _lib.WINDOW_ROUTES[rc]
+
+
 def _labels_and_mask(unc_type, pur_type, ground_truth, active, shape):
     """(gt, act): the int64 labels where the chosen types read them (None otherwise) and the uint8 form of the optional mask"""
     gt = None

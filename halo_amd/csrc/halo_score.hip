@@ -562,20 +562,15 @@ __device__ __forceinline__ int pad_index(int t, int n, int mode)
     return t < 0 ? t + n : t - n;                       // circular
 }
 
+// One pixel of the generic walk (k_region_impurity, and the tiled kernel's tiles that hold a label outside [0, bins)).
 template <typename TL>
-__global__ void __launch_bounds__(TPB) k_region_impurity(const TL *__restrict__ pred, int H, int W, int k,
-                                                         float logK, float *__restrict__ imp, float *__restrict__ count, int pad)
+__device__ __forceinline__ float region_impurity_px(const TL *__restrict__ pp, int H, int W, int k, int y, int x, int pad, float logK, float &cnt)
 {
-    const int b = blockIdx.y;
-    const long long hw = (long long)H * W;
-    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
-    if (i >= hw) return;
-    const int y = (int)(i / W), x = (int)(i % W), r = k / 2;
+    const int r = k / 2;
     // zero padding: the in-image part of the window; any other mode: the whole window, taps mapped into the image
     const int y0 = pad ? y - r : (y - r < 0 ? 0 : y - r), y1 = pad ? y + r : (y + r >= H ? H - 1 : y + r);
     const int x0 = pad ? x - r : (x - r < 0 ? 0 : x - r), x1 = pad ? x + r : (x + r >= W ? W - 1 : x + r);
-    const TL *pp = pred + (size_t)b * hw;
-    const float cnt = (float)((y1 - y0 + 1) * (x1 - x0 + 1));
+    cnt = (float)((y1 - y0 + 1) * (x1 - x0 + 1));
     ClassSum acc;
     int cur = -1;
     while (true) {
@@ -593,7 +588,20 @@ __global__ void __launch_bounds__(TPB) k_region_impurity(const TL *__restrict__ 
         acc.add(nxt, (-d) * det_logf(d + 1e-6f));
         cur = nxt;
     }
-    imp[(size_t)b * hw + i] = acc.result() / logK;
+    return acc.result() / logK;
+}
+
+template <typename TL>
+__global__ void __launch_bounds__(TPB) k_region_impurity(const TL *__restrict__ pred, int H, int W, int k,
+                                                         float logK, float *__restrict__ imp, float *__restrict__ count, int pad)
+{
+    const int b = blockIdx.y;
+    const long long hw = (long long)H * W;
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= hw) return;
+    float cnt;
+    const float res = region_impurity_px(pred + (size_t)b * hw, H, W, k, (int)(i / W), (int)(i % W), pad, logK, cnt);
+    imp[(size_t)b * hw + i] = res;
     if (count) count[(size_t)b * hw + i] = cnt;
 }
 
@@ -678,14 +686,188 @@ __global__ void __launch_bounds__(TPB) k_region_impurity3(const TL *__restrict__
     block_minmax<TPB>(mn, mx, partials + (((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2);
 }
 
+// ---------------------------------------------------------------- wide windows (5 <= k <= 33) on LDS tiles
+// The module's default window is 33 x 33 (RADIUS_K = 16).  Both window passes stage their tile with a halo of r = k / 2 into LDS
+// once -- out-of-image taps mapped by pad_index, so all four padding modes are served -- and produce the generic kernels' bits:
+// the class counts are integers (any counting order), the class sum and the box sum keep the generic kernels' order of additions.
+constexpr int WW_KMAX = 33, WW_RMAX = WW_KMAX / 2;
+constexpr int WH_TW = TPB, WH_TH = 16;                    // histogram tile: one lane per column, the rows one after the other
+constexpr int WH_BINS = 32, WH_NQ = WH_BINS / 8;          // four 16-bit counters per 64-bit word, two words per 16-byte LDS element
+constexpr int WH_CW = WH_TW + 2 * WW_RMAX, WH_LR = WH_TH + 2 * WW_RMAX;
+constexpr int WB_TW = 64, WB_TH = 32, WB_P = 8;           // box-sum tile: a lane owns WB_P consecutive pixels of a row
+constexpr int WB_LW = 100, WB_LH = WB_TH + 2 * WW_RMAX;   // row stride in floats (below), tile rows
+
+// Source index of tile coordinate t (image coordinate; t >= -r) along an axis of n pixels whose last pixel in the tile is `last`:
+// pad_index inside the span the tile's windows reach, -1 (= nothing there) beyond it, where pad_index's formulas no longer hold.
+__device__ __forceinline__ int tile_src(int t, int n, int last, int r, int pad) { return t <= last + r ? pad_index(t, n, pad) : -1; }
+
+// Which kernels serve a window pass (halo_window_route of halo_hip.h): 0 the generic one-thread-per-pixel kernels, 1 the 3 x 3
+// zero-padding tile kernels, 2 the tiled wide-window kernels below.  The launchers branch on this function and on nothing else
+// about (k, padding mode, bins, H, W).  3 x 3 under a non-zero padding mode stays generic.
+inline int window_route(int what, int k, int pad, int64_t bins, int64_t H, int64_t W)
+{
+    if (k == 3 && pad == HALO_PAD_ZEROS) {
+        if (what == HALO_WINDOW_BOX) return W % 4 == 0 ? 1 : 0;
+        return cdiv(H, RI_TH) <= 65535 ? 1 : 0;
+    }
+    if (k < 5 || k > WW_KMAX || !(k & 1)) return 0;
+    if (what == HALO_WINDOW_BOX) return cdiv(H, WB_TH) <= 65535 ? 2 : 0;
+    return (bins >= 1 && bins <= WH_BINS && cdiv(H, WH_TH) <= 65535) ? 2 : 0;
+}
+
+// k x k window class histogram, 5 <= k <= 33, at most WH_BINS bins.  A workgroup owns WH_TW columns x WH_TH rows; lane = column.
+//   lab : the (WH_TH + 2r) x (WH_TW + 2r) labels as bytes (255: a zero-padding tap, never counted)
+//   ch  : per tile column, the class counts of the k labels of that column in the current row's window, as 16-bit counters packed
+//         four to a 64-bit word (a window count is at most 1089); going down one row drops one label and adds one per column
+//   term: the <= k * k + 1 values (-d) log(d + 1e-6), d = n / k^2, of a full window, by the generic kernel's expression
+// A pixel adds the k column words of its window (16-byte LDS reads, consecutive lanes on consecutive elements) and then visits the
+// classes in ascending order.  The sum below is ClassSum's over the classes present: an absent class adds +0 to a partial sum
+// that is never -0 (it starts from +0), and ClassSum's flush between classes 15 and 16 is made whether or not either side is
+// empty, which moves a partial sum through `0 + s` -- the same bits (the argument of the comment above ClassSum).
+// A tile that stages a label outside [0, bins) (the int64 helper entry takes any labels) walks its pixels as the generic kernel does.
+template <bool FULL>
+__device__ __forceinline__ float hist_class_sum(const unsigned long long (&a)[2 * WH_NQ], int nq, const float *__restrict__ term, float cnt)
+{
+    float a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+    for (int q = 0; q < WH_NQ; ++q) {
+        if (q < nq) {                                            // kernel-uniform
+            if (q == 2) { a1 = a1 + a0; a0 = 0.0f; }             // ClassSum: classes 0-15 are flushed when class 16 arrives
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int n = (int)((a[2 * q + (e >> 2)] >> ((e & 3) * 16)) & 0xffffull);
+                float t;
+                if (FULL) t = term[n];
+                else {
+                    const float d = (float)n / cnt;
+                    t = n ? (-d) * det_logf(d + 1e-6f) : 0.0f;
+                }
+                a0 = a0 + t;
+            }
+        }
+    }
+    return ((a0 + a1) + 0.0f) + 0.0f;
+}
+
+__device__ __forceinline__ void hist_bump(unsigned long long *chw, int tx, int v, bool up)
+{
+    if (v == 255) return;
+    unsigned long long &w = chw[(((v >> 3) * WH_CW) + tx) * 2 + ((v >> 2) & 1)];
+    const unsigned long long one = 1ull << ((v & 3) * 16);
+    w = up ? w + one : w - one;
+}
+
+template <typename TL>
+__global__ void __launch_bounds__(TPB) k_region_impurity_tiled(const TL *__restrict__ pred, int H, int W, int k, int bins, float logK,
+                                                               float *__restrict__ imp, float *__restrict__ count,
+                                                               double *__restrict__ partials, int pad)
+{
+    __shared__ unsigned char lab[WH_LR][WH_CW];
+    __shared__ __attribute__((aligned(16))) unsigned long long ch[WH_NQ][WH_CW][2];
+    __shared__ float term[WW_KMAX * WW_KMAX + 1];
+    __shared__ int bad;
+    const int b = blockIdx.z, tid = threadIdx.x, r = k / 2, kk = k * k;
+    const int X0 = blockIdx.x * WH_TW, Y0 = blockIdx.y * WH_TH;
+    const int nrows = H - Y0 < WH_TH ? H - Y0 : WH_TH, ncols = W - X0 < WH_TW ? W - X0 : WH_TW;
+    const int Wt = WH_TW + 2 * r, Ht = nrows + 2 * r, nq = (bins + 7) >> 3;
+    const long long hw = (long long)H * W;
+    const TL *pp = pred + (size_t)b * hw;
+    unsigned long long *chw = &ch[0][0][0];
+    if (tid == 0) bad = 0;
+    for (int n = tid; n <= kk; n += TPB) {
+        const float d = (float)n / (float)kk;
+        term[n] = n ? (-d) * det_logf(d + 1e-6f) : 0.0f;
+    }
+    for (int e = tid; e < WH_NQ * WH_CW * 2; e += TPB) chw[e] = 0ull;
+    __syncthreads();
+    int odd = 0;
+    for (int tx = tid; tx < Wt; tx += TPB) {
+        const int xs = tile_src(X0 + tx - r, W, X0 + ncols - 1, r, pad);
+        for (int ty = 0; ty < Ht; ++ty) {
+            const int ys = tile_src(Y0 + ty - r, H, Y0 + nrows - 1, r, pad);
+            int v = 255;
+            if (xs >= 0 && ys >= 0) {
+                const long long q = (long long)pp[(size_t)ys * W + xs];
+                if (q >= 0 && q < (long long)bins) v = (int)q;
+                else odd = 1;
+            }
+            lab[ty][tx] = (unsigned char)v;
+        }
+    }
+    if (odd) bad = 1;
+    __syncthreads();
+    const bool generic = bad != 0;                               // workgroup-uniform
+    const int x = X0 + tid;
+    const bool live = tid < ncols;
+    double mn = 0.0, mx = 0.0;
+    if (!generic) {
+        for (int tx = tid; tx < Wt; tx += TPB)                   // the first row's windows: tile rows 0 .. 2r
+            for (int ty = 0; ty <= 2 * r; ++ty) hist_bump(chw, tx, lab[ty][tx], true);
+    }
+    for (int j = 0; j < nrows; ++j) {
+        const int y = Y0 + j;
+        float res = 0.0f, cnt = 0.0f;
+        if (generic) {
+            if (live) res = region_impurity_px(pp, H, W, k, y, x, pad, logK, cnt);
+        } else {
+            if (j > 0) {
+                for (int tx = tid; tx < Wt; tx += TPB) {
+                    hist_bump(chw, tx, lab[j - 1][tx], false);
+                    hist_bump(chw, tx, lab[j + 2 * r][tx], true);
+                }
+            }
+            __syncthreads();
+            if (live) {
+                unsigned long long a[2 * WH_NQ];
+#pragma unroll
+                for (int i = 0; i < 2 * WH_NQ; ++i) a[i] = 0ull;
+                for (int dx = 0; dx < k; ++dx) {
+#pragma unroll
+                    for (int q = 0; q < WH_NQ; ++q)
+                        if (q < nq) { const ulonglong2 c2 = *reinterpret_cast<const ulonglong2 *>(ch[q][tid + dx]); a[2 * q] += c2.x; a[2 * q + 1] += c2.y; }
+                }
+                int cnti = kk;
+                if (!pad) {
+                    const int y0 = y - r < 0 ? 0 : y - r, y1 = y + r >= H ? H - 1 : y + r;
+                    const int x0 = x - r < 0 ? 0 : x - r, x1 = x + r >= W ? W - 1 : x + r;
+                    cnti = (y1 - y0 + 1) * (x1 - x0 + 1);
+                }
+                cnt = (float)cnti;
+                res = (cnti == kk ? hist_class_sum<true>(a, nq, term, cnt) : hist_class_sum<false>(a, nq, term, cnt)) / logK;
+            }
+            __syncthreads();                                     // the next row's update rewrites ch
+        }
+        if (live) {
+            const size_t o = (size_t)b * hw + (size_t)y * W + x;
+            imp[o] = res;
+            if (count) count[o] = cnt;
+            if (j == 0) mn = mx = (double)res;
+            else { mn = nan_min(mn, (double)res); mx = nan_max(mx, (double)res); }
+        }
+    }
+    if (!partials) return;                                       // kernel argument: uniform
+    __shared__ double seed[2];
+    if (tid == 0) { seed[0] = mn; seed[1] = mx; }                // thread 0 (pixel X0, Y0) is always live
+    __syncthreads();
+    if (!live) { mn = seed[0]; mx = seed[1]; }
+    block_minmax<TPB>(mn, mx, partials + (((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2);
+}
+
 // Returns the number of min/max partials per image written to `partials` (0: none -- the caller runs k_minmax_f32).
 template <typename TL>
-static int launch_region_impurity(const TL *pred, int64_t B, int64_t H, int64_t W, int k, float logK, float *imp, float *count,
+static int launch_region_impurity(const TL *pred, int64_t B, int64_t H, int64_t W, int k, int64_t bins, float logK, float *imp, float *count,
                                   hipStream_t st, double *partials, int pad)
 {
-    if (pad == HALO_PAD_ZEROS && k == 3 && cdiv(H, RI_TH) <= 65535 && B <= 65535) {
+    const int route = B <= 65535 ? window_route(HALO_WINDOW_HIST, k, pad, bins, H, W) : 0;
+    if (route == 1) {
         const dim3 grid((unsigned)cdiv(W, RI_TW), (unsigned)cdiv(H, RI_TH), (unsigned)B);
         hipLaunchKernelGGL((k_region_impurity3<TL>), grid, dim3(TPB), 0, st, pred, (int)H, (int)W, logK, imp, count, partials);
+        return partials ? (int)(grid.x * grid.y) : 0;
+    }
+    if (route == 2) {
+        const dim3 grid((unsigned)cdiv(W, WH_TW), (unsigned)cdiv(H, WH_TH), (unsigned)B);
+        hipLaunchKernelGGL((k_region_impurity_tiled<TL>), grid, dim3(TPB), 0, st, pred, (int)H, (int)W, k, (int)bins, logK, imp, count,
+                           partials, pad);
         return partials ? (int)(grid.x * grid.y) : 0;
     }
     hipLaunchKernelGGL((k_region_impurity<TL>), dim3((unsigned)cdiv(H * W, TPB), (unsigned)B), dim3(TPB), 0, st, pred, (int)H, (int)W, k,
@@ -739,6 +921,101 @@ __global__ void __launch_bounds__(TPB) k_box_unc(const float *__restrict__ ent, 
     __syncthreads();
     if (!live) { mn = seed[0]; mx = seed[1]; }
     block_minmax<TPB>(mn, mx, partials + ((size_t)b * gridDim.x + blockIdx.x) * 2);
+}
+
+// k x k box sum, 5 <= k <= 33, on an LDS tile: the (WB_TH + 2r) x (WB_TW + 2r) entropies are staged once (out-of-image taps
+// mapped by pad_index; +0 under zero padding, which is what the generic kernel adds there).  A lane owns WB_P = 8 consecutive
+// pixels of a row and walks the k window rows top to bottom; in a row it adds the taps left to right into one accumulator per
+// pixel, four taps at a time from a sliding 12-value register window that one 16-byte LDS read per step refills -- the generic
+// kernel's chain of k * k rounded additions from +0, with (k + 7) / 8 LDS values read per row and pixel instead of k.
+// Lane t sits on tile row t % 32 and pixel group t / 32: the 16 lanes a ds_read_b128 services together are then on 16 different
+// rows of one column, and with a row stride of WB_LW = 100 floats (25 sixteen-byte slots: odd) they fall on 16 different slots.
+// The tail (k % 4 is 1 or 3) is a kernel-uniform branch.  Epilogue as k_box_unc: / count, per-workgroup min / max.
+__global__ void __launch_bounds__(TPB) k_box_unc_tiled(const float *__restrict__ ent, int H, int W, int k, int pk,
+                                                       float *__restrict__ unc, double *__restrict__ partials, int pad)
+{
+    static_assert(WB_TW + 2 * WW_RMAX <= WB_LW && WB_LW % 4 == 0 && (WB_LW / 4) % 2 == 1, "row stride of the box tile");
+    static_assert(WB_TW - WB_P + 4 * ((WW_KMAX - 1) / 4) + 12 <= WB_LW, "the register window's last read stays inside a tile row");
+    static_assert(WB_TH * (WB_TW / WB_P) == TPB, "one lane per row and pixel group");
+    __shared__ __attribute__((aligned(16))) float tile[WB_LH][WB_LW];
+    const int b = blockIdx.z, tid = threadIdx.x, r = k / 2;
+    const int X0 = blockIdx.x * WB_TW, Y0 = blockIdx.y * WB_TH;
+    const int nrows = H - Y0 < WB_TH ? H - Y0 : WB_TH, ncols = W - X0 < WB_TW ? W - X0 : WB_TW;
+    const int Wt = WB_TW + 2 * r, Ht = nrows + 2 * r;
+    const long long hw = (long long)H * W;
+    const float *ep = ent + (size_t)b * hw;
+    {
+        const int tx = tid & 127;
+        if (tx < Wt) {
+            const int xs = tile_src(X0 + tx - r, W, X0 + ncols - 1, r, pad);
+            for (int ty = tid >> 7; ty < Ht; ty += TPB / 128) {
+                const int ys = tile_src(Y0 + ty - r, H, Y0 + nrows - 1, r, pad);
+                tile[ty][tx] = (xs >= 0 && ys >= 0) ? ep[(size_t)ys * W + xs] : 0.0f;
+            }
+        }
+    }
+    __syncthreads();
+    const int ry = tid & (WB_TH - 1), lx = (tid / WB_TH) * WB_P;
+    const int y = Y0 + ry, xb = X0 + lx;
+    const bool live = ry < nrows && lx < ncols;
+    double mn = 0.0, mx = 0.0;
+    if (live) {
+        const int nfull = k >> 2, rem = k & 3;
+        float acc[WB_P];
+#pragma unroll
+        for (int j = 0; j < WB_P; ++j) acc[j] = 0.0f;
+        for (int dy = 0; dy < k; ++dy) {
+            const float4 *row = reinterpret_cast<const float4 *>(&tile[ry + dy][lx]);
+            float v[12];
+            { const float4 q = row[0]; v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+            { const float4 q = row[1]; v[4] = q.x; v[5] = q.y; v[6] = q.z; v[7] = q.w; }
+            for (int c = 0; c < nfull; ++c) {
+                { const float4 q = row[c + 2]; v[8] = q.x; v[9] = q.y; v[10] = q.z; v[11] = q.w; }
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int j = 0; j < WB_P; ++j) acc[j] = acc[j] + v[j + t];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = v[i + 4];
+            }
+#pragma unroll
+            for (int j = 0; j < WB_P; ++j) acc[j] = acc[j] + v[j];
+            if (rem == 3) {
+                const float4 q = row[nfull + 2];
+                v[8] = q.x; v[9] = q.y;
+#pragma unroll
+                for (int t = 1; t < 3; ++t)
+#pragma unroll
+                    for (int j = 0; j < WB_P; ++j) acc[j] = acc[j] + v[j + t];
+            }
+        }
+        bool have = false;
+#pragma unroll
+        for (int j = 0; j < WB_P; ++j) {
+            const int x = xb + j;
+            if (x < W) {
+                float cnt = 1.0f;
+                if (pk > 0 && pad) {
+                    cnt = (float)(pk * pk);                    // padded taps are image pixels: the purity window is always full
+                } else if (pk > 0) {
+                    const int pr = pk / 2;
+                    const int y0 = y - pr < 0 ? 0 : y - pr, y1 = y + pr >= H ? H - 1 : y + pr;
+                    const int x0 = x - pr < 0 ? 0 : x - pr, x1 = x + pr >= W ? W - 1 : x + pr;
+                    cnt = (float)((y1 - y0 + 1) * (x1 - x0 + 1));
+                }
+                const float a = acc[j] / cnt;
+                unc[(size_t)b * hw + (size_t)y * W + x] = a;
+                if (!have) { mn = mx = (double)a; have = true; }
+                else { mn = nan_min(mn, (double)a); mx = nan_max(mx, (double)a); }
+            }
+        }
+    }
+    if (!partials) return;
+    __shared__ double seed[2];
+    if (tid == 0) { seed[0] = mn; seed[1] = mx; }                   // thread 0 (pixel X0, Y0) is always live
+    __syncthreads();
+    if (!live) { mn = seed[0]; mx = seed[1]; }
+    block_minmax<TPB>(mn, mx, partials + (((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2);
 }
 
 // 3 x 3 fast path (the only window the reference's drivers use: RADIUS_K = 1, build.py:83-88):
@@ -2099,6 +2376,8 @@ static void launch_feat(const T *feat, long long bstride, int C, long long hw, i
 using namespace halo;
 
 static_assert(RI_TW == LR_TW && RI_TH == LR_TH, "k_region_impurity3 writes one min/max partial per tile of the same shape");
+static_assert(WB_TW % LR_TW == 0 && WB_TH % LR_TH == 0 && WH_TW % LR_TW == 0 && WH_TH % LR_TH == 0,
+              "a wide-window tile is a union of whole 64 x 16 tiles: one partial per tile never needs more slots than those");
 static size_t partial_slots(int64_t H, int64_t W)
 {
     const size_t a = (size_t)cdiv(H * W, FTPB), b = (size_t)(cdiv(W, LR_TW) * cdiv(H, LR_TH));
@@ -2447,7 +2726,7 @@ static int launch_tail(const halo_score_args &a, ScorePlan &p, hipStream_t st)
     // a separate pass for the other sources of the map, nothing at all when the branch does not normalise (ripu.yaml)
     if (p.hist) {
         const float logK = (float)log((double)(a.pur_type == HALO_PUR_HYPER ? a.K : a.O));
-        const int np = launch_region_impurity<short>((const short *)p.pred, B, H, W, a.pksize, logK, (float *)p.imp_raw, (float *)nullptr, st,
+        const int np = launch_region_impurity<short>((const short *)p.pred, B, H, W, a.pksize, a.pur_type == HALO_PUR_HYPER ? a.K : a.O, logK, (float *)p.imp_raw, (float *)nullptr, st,
                                                      normalize ? p.part_imp : nullptr, p.pad);
         p.nblk_imp = np ? np : p.nblk1;
         if (normalize && !np) hipLaunchKernelGGL(k_minmax_f32, grid1, block, 0, st, (const float *)p.imp_raw, hw, p.part_imp);
@@ -2459,7 +2738,8 @@ static int launch_tail(const halo_score_args &a, ScorePlan &p, hipStream_t st)
 
     // ---- box-sum of the uncertainty, / count
     const int do_box = (a.unc_type == HALO_UNC_ENTROPY || a.unc_type == HALO_UNC_ORACLE_ACC) ? 1 : 0;
-    const bool box3 = do_box && p.pad == HALO_PAD_ZEROS && a.ksize == 3 && W % 4 == 0 && aligned16(p.ent) && aligned16(p.unc_raw);   // (the 3x3 fast paths pad with zeros)
+    const int box_route = do_box ? window_route(HALO_WINDOW_BOX, a.ksize, p.pad, 0, H, W) : 0;
+    const bool box3 = box_route == 1 && aligned16(p.ent) && aligned16(p.unc_raw);   // (the 3x3 fast paths pad with zeros)
     // 3 x 3 window + 16-byte aligned maps: the box sum is recomputed inside the combine kernel (no stored copy); otherwise the
     // round-2 sequence (k_box3_unc / k_box_unc + k_combine, identical results)
     const bool fuse_tail = box3 && B <= 65535 && H <= 65535 && aligned16(p.imp_raw) && aligned16(a.score) && (!a.impurity || aligned16(a.impurity)) &&
@@ -2480,6 +2760,11 @@ static int launch_tail(const halo_score_args &a, ScorePlan &p, hipStream_t st)
         p.nblk_unc = (int)cdiv(hw, TPB * 4);
         hipLaunchKernelGGL(k_box3_unc, dim3((unsigned)p.nblk_unc, (unsigned)B), block, 0, st, (const float *)p.ent, (int)H, (int)W, box_pk, p.unc_raw,
                            normalize ? p.part_unc : nullptr);
+    } else if (box_route == 2) {
+        const dim3 gridw((unsigned)cdiv(W, WB_TW), (unsigned)cdiv(H, WB_TH), (unsigned)B);
+        p.nblk_unc = (int)(gridw.x * gridw.y);
+        hipLaunchKernelGGL(k_box_unc_tiled, gridw, block, 0, st, (const float *)p.ent, (int)H, (int)W, a.ksize, box_pk, p.unc_raw,
+                           normalize ? p.part_unc : nullptr, p.pad);
     } else {
         hipLaunchKernelGGL(k_box_unc, grid1, block, 0, st, p.ent, (int)H, (int)W, a.ksize, do_box, box_pk, p.unc_raw, normalize ? p.part_unc : nullptr, p.pad);
     }
@@ -2565,7 +2850,11 @@ extern "C" int halo_region_uncertainty(const float *x, int64_t bstride, int is_p
     else
         hipLaunchKernelGGL(k_logit_maps_generic, grid1, block, 0, st, x, (long long)bstride, (const long long *)gt, (int)O, hw,
                            unc_type, HALO_PUR_NONE, is_prob, dst, (short *)nullptr);
-    if (do_box)
+    // (a 3 x 3 window stays on the generic kernel here: the 3 x 3 tile kernels belong to halo_score's tail)
+    if (do_box && window_route(HALO_WINDOW_BOX, ksize, pad, 0, H, W) == 2)
+        hipLaunchKernelGGL(k_box_unc_tiled, dim3((unsigned)cdiv(W, WB_TW), (unsigned)cdiv(H, WB_TH), (unsigned)B), block, 0, st, (const float *)ent,
+                           (int)H, (int)W, ksize, 0, out, (double *)nullptr, pad);
+    else if (do_box)
         hipLaunchKernelGGL(k_box_unc, grid1, block, 0, st, (const float *)ent, (int)H, (int)W, ksize, 1, 0, out, (double *)nullptr, pad);
     return check_launch("halo_region_uncertainty");
 }
@@ -2577,9 +2866,19 @@ extern "C" int halo_region_impurity(const int64_t *pred, int64_t B, int64_t H, i
     if (!pred || !impurity || B <= 0 || H <= 0 || W <= 0 || K < 1) return fail(HALO_E_ARG, "halo_region_impurity: null/empty argument");
     if (ksize < 1 || !(ksize & 1)) return fail(HALO_E_ARG, "halo_region_impurity: window size must be odd");
     { const int rc = check_padding(pad_mode, ksize, H, W, "halo_region_impurity"); if (rc != HALO_OK) return rc; }
-    launch_region_impurity<long long>((const long long *)pred, B, H, W, ksize, (float)log((double)K), impurity, count, (hipStream_t)stream,
+    launch_region_impurity<long long>((const long long *)pred, B, H, W, ksize, K, (float)log((double)K), impurity, count, (hipStream_t)stream,
                                       nullptr, pad_mode);
     return check_launch("halo_region_impurity");
+}
+
+// Which kernels serve a window pass of this shape (halo_hip.h); the launchers above branch on the same function.
+extern "C" int halo_window_route(int what, int ksize, int pad_mode, int64_t bins, int64_t H, int64_t W)
+{
+    if (what != HALO_WINDOW_BOX && what != HALO_WINDOW_HIST) return fail(HALO_E_ARG, "halo_window_route: unknown window pass %d", what);
+    if (ksize < 1 || !(ksize & 1)) return fail(HALO_E_ARG, "halo_window_route: window size must be odd");
+    if (pad_mode < HALO_PAD_ZEROS || pad_mode > HALO_PAD_CIRCULAR) return fail(HALO_E_ARG, "halo_window_route: bad padding mode %d", pad_mode);
+    if (H <= 0 || W <= 0) return fail(HALO_E_ARG, "halo_window_route: empty map");
+    return window_route(what, ksize, pad_mode, bins, H, W);
 }
 
 // FloatingRegionScore.quantize_uncert_map(decoder_out) (floating_region.py:94-110) -> int64 bins

@@ -244,6 +244,13 @@ int halo_region_uncertainty(const float *x, int64_t bstride, int is_prob, const 
                             size_t workspace_bytes, void *stream);
 int halo_region_impurity(const int64_t *pred, int64_t B, int64_t H, int64_t W, int ksize, int64_t K, float *impurity,
                          float *count, int pad_mode, void *stream);
+/* Which kernels serve a k x k window pass -- the box sum of the uncertainty (HALO_WINDOW_BOX) or the class histogram of the purity
+ * window (HALO_WINDOW_HIST; bins = classes, or K for 'hyper') -- on an H x W map: 0 the generic one-thread-per-pixel kernels, 1 the
+ * 3 x 3 zero-padding tile kernels of the scorer, 2 the LDS-tiled wide-window kernels (odd k from 5 to 33, every padding mode,
+ * at most 32 bins).  A pure host function: the launchers branch on it.  Every route computes the same bits.  <0: HALO_E_ARG. */
+#define HALO_WINDOW_BOX 0
+#define HALO_WINDOW_HIST 1
+int halo_window_route(int what, int ksize, int pad_mode, int64_t bins, int64_t H, int64_t W);
 int halo_quantize_radius(const void *feat, int feat_dtype, int64_t feat_bstride, int64_t B, int64_t C, int64_t H,
                          int64_t W, int64_t K, double c, int64_t *pred, void *workspace, size_t workspace_bytes,
                          void *stream);
