@@ -2,6 +2,7 @@
 """bench.py -- acquisition-scored images/s on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W      # N > 1 without a launcher: starts the N ranks itself
+    python bench.py --gpus N --steps K --warmup W --full      # the same run + everything else this file measures and checks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -25,8 +26,19 @@ DESIGN.md / profiles/, not the BASELINE unit.
 maps) as .npy files, so that two builds can be compared output for output on the same seeded inputs.
 
 Prints ONE JSON line (rank 0).  roofline: the feature-reduction kernel's algorithmic bytes / its
-average duration measured live with HIP events on its own stream.  cpu_baseline: the CPU oracle
-(OpenMP over the host cores this process may use) on 1 warm-up + 8 of the same images (kind "port").
+average duration, from the HIP events the timed steps record around it on its own stream anyway.
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps, the pipeline's own
+consistency asserts (milliseconds: the slots' restored state, repeated ring images giving repeated tables, what the
+exchange delivered), --dump-outputs, the line.  `--full` (`"full": true` in the line) adds every measurement that takes a
+run of its own, after the timed region and after the arrays to dump are taken (images/s, ms_per_step and the dump are the
+same either way):
+  * cpu_baseline / speedup_vs_cpu: the CPU oracle (OpenMP over the host cores this process may use) on 1 warm-up +
+    `--cpu-images` (8) of the same images (kind "port"), and parity_vs_cpu: the TIMED launches' pick tables against the
+    oracle's for those images -- a mismatch exits non-zero;
+  * roofline.flat_read: a flat non-temporal read of one launch's feature tensors, alone (null in a plain run);
+  * roofline.traffic / traffic_from_profile: the kernel's HBM traffic from counter passes (HALO_BENCH_PMC, profiles/);
+  * roofline.scoring_call_alone_ms_per_batch, with HALO_BENCH_BATCH_ALONE set.
 """
 import argparse
 import json
@@ -82,7 +94,11 @@ def parse():
                     help="--source lowres only: 'exact' (the product's default) interpolates every channel, bit-identical to "
                          "upsample-then-score; 'gram' (opt-in) evaluates a float64 embedding's radius through per-cell Gram terms "
                          "(SURVEY 8f N1), guarded against cancellation")
-    ap.add_argument("--cpu-images", type=int, default=8, help="timed images in the CPU-baseline sample, after one "
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the CPU baseline and the oracle "
+                         "check of the timed pick tables (--cpu-images), the flat-read probe, the counter-pass traffic figures "
+                         "(off by default: a plain run sets up, warms up, times its steps and prints its line)")
+    ap.add_argument("--cpu-images", type=int, default=8, help="--full: timed images in the CPU-baseline sample, after one "
                                                               "untimed warm-up image (0 = skip)")
     ap.add_argument("--resets", choices=["undo", "kernel", "fills", "side"], default="undo",
                     help="how a slot's round-1 state (active = selected = False, active_mask = 255: what the loader hands over in "
@@ -707,7 +723,7 @@ def main():
     lr_ms = pipe.lowres_pass_ms()
     lr_logit_ms, lr_feat_ms = lr_ms["logit"], lr_ms["feat"]
     batch_alone = None
-    if rank == 0 and not lowres and feat_ms and os.environ.get("HALO_BENCH_BATCH_ALONE"):
+    if a.full and rank == 0 and not lowres and feat_ms and os.environ.get("HALO_BENCH_BATCH_ALONE"):
         # diagnostic: the scoring call on each resident batch with nothing beside it, after the timed region
         from halo_amd.core.active.floating_region import score_maps
         batch_alone = []
@@ -721,7 +737,7 @@ def main():
             e1.record(); torch.cuda.synchronize(dev)
             batch_alone.append(round(e0.elapsed_time(e1) / 4, 3))
     flat = None
-    if rank == 0 and not lowres and feat_ms:
+    if a.full and rank == 0 and not lowres and feat_ms:
         # this box's own ceiling for the same bytes, after the timed region: a flat non-temporal read (no arithmetic, no
         # plane structure, nothing written) of the B feature tensors one k_feat_reduce launch streams, nothing beside it
         # (tools/libhalo_probe.so: a measurement aid outside the product ABI; absent -> the field is null)
@@ -765,7 +781,7 @@ def main():
         out = {
             "metric": "acquisition-scored images/sec (1024x2048, C=256, 19 cls)",
             "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "full": bool(a.full),
             "scaling": "strong" if pool_mode else "weak",       # --pool-images fixes the total work, --steps the per-GPU work
             "vs_baseline": None, "dtype": a.feat_dtype, "data": "synthetic",
             "config": {"workload": "configs[%d]: synthetic pool of %d image evaluations (%s), %dx%d, C=%d %s embedding, %d classes, %s branch "
@@ -882,7 +898,7 @@ def main():
         # call, of this exact launch shape (tools/collect_profiles.sh) -> `traffic`.  Otherwise the tracked collection's figure is
         # quoted under its own name and `traffic` stays null.
         same_run = os.environ.get("HALO_BENCH_PMC")
-        for name in ([same_run] if same_run else []) + ["r06_pmc_summary.json", "r05_pmc_summary.json"]:
+        for name in (([same_run] if same_run else []) + ["r06_pmc_summary.json", "r05_pmc_summary.json"]) if a.full else []:
             pmc = name if os.path.isabs(name) or name == same_run else os.path.join(ROOT, "profiles", name)
             if out["roofline"] is None or lowres or not os.path.exists(pmc):
                 continue
@@ -899,7 +915,7 @@ def main():
                     break
             except Exception:
                 pass
-        if a.cpu_images > 0 and world == 1:
+        if a.full and a.cpu_images > 0 and world == 1:
             slots = parity_slots(R, B, n_local, a.cpu_images)
             s_img, cores, picks_cpu = cpu_baseline(feat, logit, gt, prior, slots, n_regions, a.branch, lowres, a.lr_mode)
             out["cpu_baseline"] = {"value": round(1.0 / s_img, 4), "unit": "images/s", "cores": cores, "kind": "port",

@@ -456,3 +456,15 @@ def test_native_png_encoder_around_the_match_length_limits(tmp_path):
         _hostlib.png_gray8_write(p, a)
         b = np.array(Image.open(p))
         assert b.shape == a.shape and np.array_equal(a, b), (trial, H, W)
+
+
+def test_bench_has_the_full_option_off_by_default():
+    """bench.py parses its command line before it touches a device: --help lists --full, which takes no value."""
+    import subprocess
+    import sys
+    bench = os.path.join(ROOT, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert re.search(r"\[--full\]", r.stdout), r.stdout[:2000]
+    r = subprocess.run([sys.executable, bench, "--full=1"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr

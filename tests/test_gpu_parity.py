@@ -1757,13 +1757,14 @@ def test_empty_and_degenerate_inputs(dev):
 
 
 def test_bench_contract_on_a_small_shape(dev):
-    """bench.py prints ONE JSON line carrying the contract's keys (run on a tiny shape so it takes seconds)."""
+    """bench.py --full prints ONE JSON line carrying the contract's keys and everything measured beside the headline figure: the
+    CPU baseline, the oracle check of the timed tables, the flat-read probe (run on a tiny shape so it takes seconds)."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "64", "--width", "128", "--channels", "16",
-                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "4", "--cpu-images", "1"],
+                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "4", "--cpu-images", "1", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1784,6 +1785,38 @@ def test_bench_contract_on_a_small_shape(dev):
     sel = d["selection"]
     assert sel["images"] == 12 and 0 <= sel["handed_over"] <= sel["images"] and isinstance(sel["reasons"], dict)
     assert d["roofline"]["traffic"] is None and "12 image evaluations" in d["config"]["workload"]
+    assert d["full"] is True and rf["flat_read"]["GB/s"] > 0 and rf["frac_of_flat_read"] > 0
+
+
+def test_bench_plain_run_measures_the_headline_figure_only(dev):
+    """Without --full the same line, the roofline from the timed steps' own events included, and none of the measurements that
+    take a run of their own: no CPU baseline (--cpu-images is not looked at), no oracle check, no flat-read probe, no traffic
+    figure quoted from a counter pass."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--height", "64", "--width", "128", "--channels", "16",
+                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "4", "--cpu-images", "1"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in d, key
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/s"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    # images/s x s/step = the 4 images of a step, up to the line's rounding of both figures to three decimals
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 4) <= 4 * 1.01 * (0.0005 / d["ms_per_step"] + 0.0005 / d["value"])
+    for key in ("cpu_baseline", "speedup_vs_cpu", "parity_vs_cpu", "parity_images_checked", "parity_rows_checked"):
+        assert key not in d, key
+    rf = d["roofline"]
+    assert rf["bound"] == "hbm" and rf["launches_timed"] == 3 and rf["avg_launch_ms"] > 0
+    assert rf["flat_read"] is None and rf["frac_of_flat_read"] is None and rf["traffic"] is None
+    assert "traffic_from_profile" not in rf and rf["scoring_call_alone_ms_per_batch"] is None
+    assert d["pipeline_tables_consistent"] is True and d["selection"]["images"] == 12
 
 
 @pytest.mark.parametrize("mode", ["exact", "gram"])
@@ -1794,7 +1827,7 @@ def test_bench_lowres_source_is_oracle_checked_too(dev, mode):
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "128", "--width", "256", "--channels", "16",
-                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "8", "--cpu-images", "2", "--source", "lowres",
+                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "8", "--cpu-images", "2", "--full", "--source", "lowres",
                         "--lr-mode", mode], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -1811,7 +1844,7 @@ def test_bench_data_variants_on_a_small_shape(dev, data):
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "128", "--width", "256", "--channels", "16",
-                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "8", "--cpu-images", "4", "--data", data],
+                        "--steps", "3", "--warmup", "1", "--batch", "4", "--ring", "8", "--cpu-images", "4", "--full", "--data", data],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -2456,7 +2489,7 @@ def test_bench_pool_images_and_branches_on_a_small_shape(dev):
     from conftest import ROOT
     for extra in (["--pool-images", "22"], ["--branch", "ripu"], ["--branch", "hyper"]):
         r = _run_script([os.path.join(ROOT, "bench.py"), "--height", "64", "--width", "128", "--channels", "16", "--steps", "3",
-                         "--warmup", "1", "--batch", "4", "--ring", "8", "--cpu-images", "1"] + extra)
+                         "--warmup", "1", "--batch", "4", "--ring", "8", "--cpu-images", "1", "--full"] + extra)
         assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
         assert d["parity_vs_cpu"] is True and d["pipeline_tables_consistent"] is True, extra
@@ -2477,7 +2510,7 @@ def test_bench_dump_outputs_are_the_last_timed_steps_and_repeat(dev, tmp_path):
     got = []
     for run in ("a", "b"):
         r = _run_script([os.path.join(ROOT, "bench.py"), "--height", str(H_), "--width", str(W_), "--channels", "16", "--steps", str(steps),
-                         "--warmup", "1", "--batch", str(B_), "--ring", "8", "--cpu-images", "1",
+                         "--warmup", "1", "--batch", str(B_), "--ring", "8", "--cpu-images", "1", "--full",
                          "--dump-outputs", str(tmp_path / run), "--dump-tables", str(tmp_path / (run + ".npz"))])
         assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

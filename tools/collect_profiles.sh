@@ -34,7 +34,7 @@ prof pmc_fetch --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_f
 prof pmc_write --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 $R/bench.py --steps 3 --warmup 1 --cpu-images 0 --ring 16
 run pmc_summary.txt python3 $R/tools/distill_profiles.py $RND --pmc-only $OUT/pmc_summary.json
 export HALO_BENCH_PMC=$OUT/pmc_summary.json
-run bench_default.json $B
+run bench_default.json $B --full
 unset HALO_BENCH_PMC
 prof trace --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --cpu-images 0
 run tail_timeline.txt python3 $R/tools/tail_timeline.py $OUT/trace
@@ -46,12 +46,12 @@ for v in "f32:--feat-dtype f32" "lowres_exact:--source lowres --lr-mode exact" "
   run bench_$name.json $B --cpu-images 0 $args
 done
 for d in late_round saturated peaked late_round+saturated+peaked plateau; do
-  run bench_data_$d.json $B --cpu-images 4 --data $d
+  run bench_data_$d.json $B --full --cpu-images 4 --data $d
 done
-run bench_ripu_peaked.json $B --cpu-images 2 --branch ripu --data peaked
+run bench_ripu_peaked.json $B --full --cpu-images 2 --branch ripu --data peaked
 # the reference's DEFAULT purity under the same stress: near-tie-dense maps, each oracle-checked on 2 images
 for d in gaussian peaked late_round+saturated+peaked; do
-  run bench_hyper_data_$d.json $B --cpu-images 2 --branch hyper --data $d
+  run bench_hyper_data_$d.json $B --full --cpu-images 2 --branch hyper --data $d
 done
 for br in ripu hyper; do
   prof trace_$br --kernel-trace --stats --output-format csv -d $OUT/trace_$br -- python3 $R/bench.py --branch $br --cpu-images 0 --steps 8 --warmup 2
@@ -61,7 +61,7 @@ prof trace_lowres --kernel-trace --stats --output-format csv -d $OUT/trace_lowre
 prof trace_lowres_gram --kernel-trace --stats --output-format csv -d $OUT/trace_lowres_gram -- python3 $R/bench.py --source lowres --lr-mode gram --cpu-images 0 --steps 8 --warmup 2
 # the default line four more times, consecutive processes WITHOUT the settle wait: they alternate between two plateaus
 for rep in 1 2 3 4; do
-  $B --cpu-images 0 --settle 0 2> /dev/null | python3 -c "
+  $B --full --cpu-images 0 --settle 0 2> /dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('run $rep: %.1f images/s  ms_per_step %.3f  k_feat_reduce %.3f ms (frac %.4f)  rest of the step %.3f ms  flat read of the same tensors %.0f GB/s' % (d['value'], d['ms_per_step'], r['avg_launch_ms'], r['frac'], d['ms_per_step'] - r['avg_launch_ms'], r['flat_read']['GB/s']))" >> $OUT/bench_repeats.txt
 done
 # (built in the container, travels with the snapshot: hipcc --offload-arch=gfx950 -O3 tools/micro/coissue.hip -o tools/micro/coissue)
