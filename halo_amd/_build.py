@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(CSRC, "libhalo_hip.so")
-SOURCES = ["halo_api.hip", "halo_score.hip", "halo_select.hip", "halo_select_binned.hip", "halo_hyperbolic.hip", "halo_loss.hip", "halo_pool.hip", "halo_eval.hip", "halo_train_loss.hip", "halo_hfr.hip", "halo_resize.hip", "halo_dwconv.hip", "halo_norm.hip", "halo_maxpool.hip"]
+SOURCES = ["halo_api.hip", "halo_score.hip", "halo_select.hip", "halo_select_binned.hip", "halo_hyperbolic.hip", "halo_loss.hip", "halo_pool.hip", "halo_eval.hip", "halo_train_loss.hip", "halo_hfr.hip", "halo_resize.hip", "halo_dwconv.hip", "halo_norm.hip", "halo_maxpool.hip", "halo_optim.hip"]
 HOST_SO = os.path.join(CSRC, "libhalo_host.so")          # plain C host helpers (PNG writer of the persistence step), built with gcc
 HOST_SOURCES = ["halo_host.c"]
 HEADERS = ["halo_common.hpp", "halo_norm_dev.hpp", "halo_devmath.hpp", "halo_softmax.hpp", "halo_select_common.hpp", "halo_select_plan.hpp", os.path.join("..", "..", "include", "halo_hip.h")]

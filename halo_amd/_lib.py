@@ -48,6 +48,20 @@ class ScoreArgs(C.Structure):
                 ("ev_tail_stop", _vp)]
 
 
+SGD_GEOOPT, SGD_TORCH = 0, 1                                        # HALO_SGD_*: halo_sgd_args.mode
+
+
+class SgdTensor(C.Structure):
+    """halo_sgd_tensor of include/halo_hip.h"""
+    _fields_ = [("p", _vp), ("g", _vp), ("buf", _vp), ("n", _i64), ("dtype", _int), ("first", _int)]
+
+
+class SgdArgs(C.Structure):
+    """halo_sgd_args of include/halo_hip.h, field for field (tests/test_optim_host.py compiles the header and compares the layouts)"""
+    _fields_ = [("struct_bytes", _sz), ("mode", _int), ("nesterov", _int), ("lr", _dbl), ("momentum", _dbl), ("dampening", _dbl),
+                ("weight_decay", _dbl), ("count", _i64), ("tensors", C.POINTER(SgdTensor))]
+
+
 # name -> (restype, argtypes); must list every symbol include/halo_hip.h declares
 SIGNATURES = {
     "halo_version": (_int, []),
@@ -116,6 +130,9 @@ SIGNATURES = {
     "halo_pool_fold_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
     "halo_maxpool_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "halo_maxpool_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "halo_sgd_plan_limits": (_int, [C.POINTER(_i64), C.POINTER(_i64)]),
+    "halo_sgd_plan": (_int, [C.POINTER(_i64), _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "halo_sgd_step": (_int, [C.POINTER(SgdArgs), _vp]),
     "halo_event_create": (_vp, []),
     "halo_event_record": (_int, [_vp, _vp]),
     "halo_event_elapsed_ms": (_int, [_vp, _vp, C.POINTER(C.c_float)]),

@@ -278,6 +278,49 @@ def use_fused_training_losses(learner_cls):
     return learner_cls
 
 
+# ---------------------------------------------------------------- the optimiser step in one HIP pass per param group
+# configure_optimizers (core/train_learners.py:167-208) builds two geoopt RiemannianSGD instances with MODEL.HYPER (two
+# torch.optim.SGD without) and their schedulers; the learners' steps then call opt.step() on each.  geoopt's step is a Python loop
+# of eight tensor statements per parameter.  `use_fused_optimizer_step(learner_cls)` binds a configure_optimizers that calls the
+# inherited one and passes every optimiser it returns through halo_amd.optim.fuse_step: the same objects, so the schedulers --
+# returned untouched -- and Lightning's bookkeeping keep pointing at them.  What fuse_step does not serve keeps its stock step.
+
+def _fuse_configured(configured):
+    """fuse_step on every optimiser of a configure_optimizers result, in any of the shapes Lightning accepts: one optimiser, a
+    list / tuple of them, the (optimisers, schedulers) pair, a dict or dicts with an "optimizer" key"""
+    from .optim import fuse_step
+    if isinstance(configured, torch.optim.Optimizer):
+        return fuse_step(configured)
+    if isinstance(configured, dict):
+        if isinstance(configured.get("optimizer"), torch.optim.Optimizer):
+            fuse_step(configured["optimizer"])
+        return configured
+    if isinstance(configured, (list, tuple)):
+        if len(configured) == 2 and isinstance(configured[0], (list, tuple)):
+            _fuse_configured(configured[0])                          # (optimisers, schedulers): the schedulers stay as they are
+        else:
+            for item in configured:
+                _fuse_configured(item)
+    return configured
+
+
+def fused_configure_optimizers(self):
+    return _fuse_configured(type(self)._unfused_configure_optimizers(self))
+
+
+def use_fused_optimizer_step(learner_cls):
+    """Bind fused_configure_optimizers on a learner class: the inherited configure_optimizers runs as before and every optimiser
+    it returns is converted by halo_amd.optim.fuse_step.  Returns the class; the method it replaced is kept as
+    `_unfused_configure_optimizers`.  Idempotent."""
+    if not isinstance(learner_cls, type) or _inherited(learner_cls, "configure_optimizers") is None:
+        raise TypeError("use_fused_optimizer_step: %r is not a class with a configure_optimizers method" % (learner_cls,))
+    if _inherited(learner_cls, "configure_optimizers") is fused_configure_optimizers:      # bound here or on a base already
+        return learner_cls
+    learner_cls._unfused_configure_optimizers = _inherited(learner_cls, "configure_optimizers")
+    learner_cls.configure_optimizers = fused_configure_optimizers
+    return learner_cls
+
+
 # ---------------------------------------------------------------- HFR weighted normalisation of the v3+ head
 # With cfg.MODEL.HFR the DeepLab-v3+ hyperbolic head runs the `wn_mlp` weighted normalisation between conv_reduce and
 # mapper.expmap (core/models/classifier.py:529-550), as torch statements.  `use_fused_feature_reweighting(head_cls)` binds

@@ -608,6 +608,54 @@ int halo_maxpool_affine_relu_fwd(const float *x, const float *scale, const float
 int halo_maxpool_affine_relu_bwd(const float *g, const uint8_t *tap, const float *scale, float *g_x, int64_t B, int64_t C, int64_t H,
                                  int64_t W, void *stream);
 
+/* ---- the optimiser step of one param group: RiemannianSGD on the Euclidean manifold and torch.optim.SGD (halo_amd/optim.py) ----
+ *  One call covers a list of tensors that share their hyper-parameters.  Per tensor: p, g, buf dense arrays of n elements of dtype
+ *  HALO_F32 | HALO_F64 (both may occur in one list), and `first`: this parameter has no momentum buffer yet.  In T = the tensor's
+ *  dtype, every scalar cast to T once:
+ *    HALO_SGD_GEOOPT  g1 = fma(wd, p, g), always (wd = 0 with p = +-inf gives NaN), stored to g;
+ *                     momentum > 0: b0 = first ? g : buf (the raw gradient, no clone pass), b1 = fma(1 - dampening, g1, fl(b0 momentum))
+ *                     stored to buf; nesterov: g2 = fma(momentum, b1, g1) stored to g, d = g2; else d = b1;  momentum <= 0: d = g1;
+ *                     p = fl(p + fl(-lr d))                            two roundings
+ *    HALO_SGD_TORCH   g1 = wd != 0 ? fma(wd, p, g) : g, g is not written;
+ *                     momentum != 0: b1 = first ? g1 : fma(1 - dampening, g1, fl(buf momentum)) stored to buf;
+ *                     d = nesterov ? fma(momentum, b1, g1) : b1;  momentum == 0: d = g1;
+ *                     p = fma(-lr, d, p)                               one rounding
+ *  The bits of geoopt.optim.RiemannianSGD.step for plain parameters and of torch.optim.SGD.step (maximize = False), denormals kept.
+ *  buf is neither read nor written without momentum (it may be NULL) and not read on a first use.  p, g and buf must not overlap.
+ *  A workgroup owns one chunk of one tensor; the table of a launch travels in the kernel arguments, `cap` tensors per launch, so
+ *  the call launches ceil(tensors of n > 0 / cap) kernels, allocates nothing, reads nothing back, never synchronises and keeps no
+ *  pointer: a host many steps ahead is fine.  A tensor whose three pointers are 16-byte aligned moves 16 bytes per lane, any
+ *  other one element per lane: same statements, same bits.  Plain stores, no atomics, no LDS.  Every check comes before the first
+ *  launch.  HALO_E_ARG: a descriptor of another size, an unknown mode, n < 0, a missing pointer of a tensor with n > 0, nesterov
+ *  without momentum; HALO_E_UNSUPPORTED: n >= 2^31, another dtype.
+ *  halo_sgd_plan_limits: the chunk's elements and cap.  halo_sgd_plan: the launch each tensor of a size list falls in (-1: n = 0,
+ *  in none) and its first block there; its blocks follow one another, block c of a tensor covers elements c chunk ..
+ *  min(n, (c + 1) chunk) - 1, and a launch's tensors fill its grid in list order.  Both are pure host functions. */
+#define HALO_SGD_GEOOPT 0
+#define HALO_SGD_TORCH 1
+typedef struct halo_sgd_tensor {
+    void *p;
+    void *g;
+    void *buf;
+    int64_t n;
+    int dtype;
+    int first;
+} halo_sgd_tensor;
+typedef struct halo_sgd_args {
+    size_t struct_bytes;            /* sizeof(halo_sgd_args) as the caller compiled it; anything else: HALO_E_ARG */
+    int mode;
+    int nesterov;
+    double lr;
+    double momentum;
+    double dampening;
+    double weight_decay;
+    int64_t count;
+    const halo_sgd_tensor *tensors; /* host array of `count` entries, read during the call only */
+} halo_sgd_args;
+int halo_sgd_plan_limits(int64_t *chunk, int64_t *cap);
+int halo_sgd_plan(const int64_t *n, int64_t count, int64_t *launch_of, int64_t *first_block, int64_t *launches);
+int halo_sgd_step(const halo_sgd_args *a, void *stream);
+
 /* ---- measurement helpers (HIP events in the same runtime the kernels are launched through) ---- */
 void *halo_event_create(void);
 int halo_event_record(void *event, void *stream);
