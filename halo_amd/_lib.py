@@ -11,6 +11,7 @@ from . import _build
 
 F32, F64 = 0, 1
 I64, I32, U8 = 2, 3, 4                                              # HALO_I64 / HALO_I32 / HALO_U8: label and prediction maps
+F16, BF16 = 5, 6                                                    # HALO_F16 / HALO_BF16: half operands of the autocast norm passes
 UNC = {"entropy": 0, "pixel_entropy": 1, "oracle_acc": 2}          # everything else -> zeros (3)
 UNC_ZEROS = 3
 PUR = {"ripu": 0, "oracle_ripu": 1, "hyper": 2, "none": 3, "radius": 4, "euc_norm": 5}
@@ -120,6 +121,8 @@ SIGNATURES = {
     "halo_affine_relu_fwd":(_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_fork_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "halo_autocast_norm_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _vp]),
+    "halo_autocast_norm_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _vp]),
     "halo_masked_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_masked_affine_relu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "halo_dropout_pair_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),

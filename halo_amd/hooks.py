@@ -580,31 +580,58 @@ def use_folded_image_pooling(head_cls):
 _RESIDUAL_ATTRS = ("conv1", "bn1", "conv2", "bn2", "relu", "downsample")
 
 
+def _norm_relu_either(x, bn, residual=None, residual_bn=None, outputs="float"):
+    """halo_amd.norm.norm_relu_autocast where its envelope holds (under torch.autocast, x the half a convolution returned: "half"
+    hands the next convolution what autocast's cast would), halo_amd.norm.norm_relu otherwise"""
+    from .norm import autocast_fallback_reason, norm_relu, norm_relu_autocast
+    if autocast_fallback_reason(x, bn, residual, residual_bn, outputs) is None:
+        return norm_relu_autocast(x, bn, residual, residual_bn, outputs)
+    return norm_relu(x, bn, residual, residual_bn)
+
+
 def residual_body(self, x, identity, fork):
     """a residual block on input x with `identity` as what a block without a downsample adds (x itself, or the second tensor of a
     forked predecessor: the same values); returns (y, y_id), the output twice -- halo_amd.norm.norm_relu_fork's pair when `fork`,
-    the same tensor object otherwise"""
-    from .norm import norm_relu, norm_relu_fork
+    the same tensor object otherwise.  Under torch.autocast, where halo_amd.norm.norm_relu_autocast serves them, the results of bn1
+    and bn2, which a convolution alone reads, are half inside the block; its output is the stock model's float32."""
+    return _residual_body(self, x, identity, fork, False)
+
+
+def _residual_body(self, x, identity, fork, half_fork):
+    """residual_body; half_fork: the successor is a bound block, which reads its input with conv1 and, as `identity`, with its tail or
+    its downsample.  Under torch.autocast, where halo_amd.norm.norm_relu_autocast serves the tail, return (y16, y32) from that
+    operator's two-output node: y16 what autocast's cast of y32 would hand conv1, y32 the block's output as the stock model has it.
+    y16 has that one reader: a second convolution on it would have the engine add two gradients in half, where the stock model,
+    which casts once per convolution, adds them in float32 -- so a downsample reads `identity` and autocast casts it as before."""
+    from .norm import autocast_fallback_reason, norm_relu_autocast, norm_relu_fork
     if type(self.relu) is not torch.nn.ReLU:
         y = self._unfused_forward(x)
         return y, y
-    out = norm_relu(self.conv1(x), self.bn1)
+    out = _norm_relu_either(self.conv1(x), self.bn1, outputs="half")
     if getattr(self, "conv3", None) is not None:             # the Bottleneck form
-        out = norm_relu(self.conv2(out), self.bn2)
+        out = _norm_relu_either(self.conv2(out), self.bn2, outputs="half")
         out, last = self.conv3(out), self.bn3
     else:                                                    # the BasicBlock form
         out, last = self.conv2(out), self.bn2
     down = self.downsample
     if down is None:
         residual, residual_bn = identity, None
-    elif type(down) is torch.nn.Sequential and len(down) == 2 and isinstance(down[0], torch.nn.Conv2d):
-        residual, residual_bn = down[0](x), down[1]          # the downsample norm is folded into the pass
+    elif _is_conv_norm(down):
+        residual, residual_bn = down[0](identity), down[1]   # the downsample norm is folded into the pass
     else:
-        residual, residual_bn = down(x), None
+        residual, residual_bn = down(identity), None
+    if half_fork and autocast_fallback_reason(out, last, residual, residual_bn, "both") is None:
+        y32, y16 = norm_relu_autocast(out, last, residual, residual_bn, outputs="both")
+        return y16, y32
     if fork:
         return norm_relu_fork(out, last, residual=residual, residual_bn=residual_bn)
-    y = norm_relu(out, last, residual=residual, residual_bn=residual_bn)
+    y = _norm_relu_either(out, last, residual, residual_bn)
     return y, y
+
+
+def _is_conv_norm(down):
+    """a downsample of the form nn.Sequential(conv, norm)"""
+    return type(down) is torch.nn.Sequential and len(down) == 2 and isinstance(down[0], torch.nn.Conv2d)
 
 
 def fused_residual_forward(self, x):
@@ -653,6 +680,7 @@ class _ChainWalk:
 
     def __call__(self, x):
         from torch.nn.modules import module as M
+        from .norm import _autocast_dtype
         box = self.box
         blocks = list(box._modules.values())
         hooked = any(b._forward_hooks or b._forward_pre_hooks for b in blocks) or bool(
@@ -661,8 +689,14 @@ class _ChainWalk:
             return torch.nn.Sequential.forward(box, x)
         identity = x
         for i, block in enumerate(blocks):
-            fork = type(block.relu) is torch.nn.ReLU and i + 1 < len(blocks) and _forks_into(blocks[i + 1])
-            x, identity = residual_body(block, x, identity, fork)
+            inner = type(block.relu) is torch.nn.ReLU and i + 1 < len(blocks)
+            fork = inner and _forks_into(blocks[i + 1])
+            # under torch.autocast a bound successor with an nn.ReLU takes (half, float32): residual_body reads the first with conv1
+            # alone and the second as the identity or with the downsample
+            if inner and _autocast_dtype() is not None and type(blocks[i + 1].relu) is torch.nn.ReLU:
+                x, identity = _residual_body(block, x, identity, fork, True)
+            else:
+                x, identity = residual_body(block, x, identity, fork)
         return x
 
 
@@ -716,8 +750,10 @@ class _PairNorm:
         self.norm = norm
 
     def __call__(self, x):
-        from .norm import fallback_reason, fused_norm_relu
+        from .norm import autocast_fallback_reason, fallback_reason, fused_norm_relu, norm_relu_autocast
         norm = self.norm
+        if autocast_fallback_reason(x, norm) is None:      # under torch.autocast: float32 out, a container's reader is not known
+            return norm_relu_autocast(x, norm)
         if fallback_reason(x, norm) is not None:
             return F.relu(type(norm).forward(norm, x), inplace=True)
         return fused_norm_relu(x, norm)

@@ -51,8 +51,10 @@ _cache = weakref.WeakKeyDictionary()          # norm module -> (the four keyed b
 # device launches issued by this module (tests count them): "fwd" / "bwd" of norm_relu, "masked_fwd" / "masked_bwd" of
 # norm_relu_dropout2d's own kernels, "pair_fwd" / "pair_bwd" of norm_relu_dropout2d_pair's, "pool_fwd" / "pool_bwd" of
 # norm_relu_maxpool's ("pool_taps": the pool_fwd launches that kept the tap codes for a backward), "fork_bwd" of norm_relu_fork's
-# two-gradient backward (its forward and its one-gradient backward are norm_relu's launches and count as "fwd" / "bwd")
-launches = {"fwd": 0, "bwd": 0, "fork_bwd": 0, "masked_fwd": 0, "masked_bwd": 0, "pair_fwd": 0, "pair_bwd": 0, "pool_fwd": 0, "pool_bwd": 0, "pool_taps": 0}
+# two-gradient backward (its forward and its one-gradient backward are norm_relu's launches and count as "fwd" / "bwd"), "ac_fwd" /
+# "ac_bwd" of norm_relu_autocast's
+launches = {"fwd": 0, "bwd": 0, "fork_bwd": 0, "masked_fwd": 0, "masked_bwd": 0, "pair_fwd": 0, "pair_bwd": 0, "pool_fwd": 0, "pool_bwd": 0, "pool_taps": 0,
+            "ac_fwd": 0, "ac_bwd": 0}
 # A speed rule, not a correctness rule (both sides return the same bits).  When a gradient will be asked for, a forward + backward
 # pair through the Python autograd node costs about 0.16 ms of host time whatever the size; measured alone, back to back, the stock
 # chain's pair is shorter than that below these element counts (2 x 512 x 80 x 160 loses without a residual_bn
@@ -526,6 +528,162 @@ def fused_norm_relu_maxpool(x, bn):
     return _NormReluPoolFn.apply(x, scale, shift, bool(torch.is_grad_enabled() and x.requires_grad))
 
 
+# ---------------------------------------------------------------- the block tail under torch.autocast
+# Under autocast the convolution in front returns half (float16 or bfloat16), FrozenBatchNorm2d's `x * scale + bias` over float32
+# buffers promotes to float32, the in-place ReLU and `out += identity` stay float32, and the next convolution has autocast round
+# that float32 tensor to half with a kernel of its own.  norm_relu_autocast runs the chain in one pass with every operand in its own
+# element type (halo_norm_autocast.hip): half -> float is exact, the statements are norm_relu's, and the half output is the
+# round-to-nearest-even half of the float32 result -- what autocast's cast hands the next convolution.  The backward is autograd's
+# for the chain plus the casts: g = g32, float(g16) or fl(g32 + float(g16)), gp = s <= 0 ? 0 : g, g_x = half(fl(gp * scale)),
+# g_r = gp for a float32 identity or half(fl(gp * r_scale)) for a downsample convolution's half output.
+
+OUTPUTS = ("float", "half", "both")
+_HALF_CODES = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+# norm_relu_autocast's own speed rule, of the same kind as AUTOGRAD_MIN_ELEMENTS (constants of its own, not copies of the float32
+# thresholds: the stock chain under autocast moves 28 to 42 bytes per element where the float32 chain moves 20 to 32): below these
+# element counts an x that needs a gradient runs the stock statements; without a gradient every size is served.  Keyed by
+# `outputs`, or "affine" with a residual_bn.  Each is the smallest size timed at which forward + backward won in every process
+# (profiles/r29_time_autocast_norm.txt: two processes over all shapes, four more over "both"): "half" from
+# 2 x 128 x 80 x 160 (x1.3 to x1.4), "float" and the half residual from 2 x 512 x 80 x 160 (x1.9 to x3.2; nothing smaller was timed),
+# "both" from 2 x 1024 x 80 x 160 -- at 2 x 512 x 80 x 160 it won x2.3 and x2.4 in the two processes and lost x0.96 in one of the four
+# further ones, on a host that took 0.2 ms for the pair of autograd nodes.  Set every value to 0 to serve every size.
+AUTOCAST_AUTOGRAD_MIN_ELEMENTS = {"half": 2 * 128 * 80 * 160, "float": 2 * 512 * 80 * 160, "both": 2 * 1024 * 80 * 160, "affine": 2 * 512 * 80 * 160}
+
+
+def _autocast_dtype():
+    """the device's autocast dtype when autocast is on there, else None"""
+    try:
+        return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+    except TypeError:                                      # torch without the device-type argument
+        return torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None
+
+
+def autocast_statement(x, bn, residual=None, residual_bn=None, outputs="float"):
+    """torch_statement under the current autocast state, plus `.to(x.dtype)` for the half output: y32, y16 or (y32, y16).  The
+    fallback of norm_relu_autocast and the oracle of its tests."""
+    if outputs not in OUTPUTS:
+        raise ValueError("outputs is %r, not one of %s" % (outputs, ", ".join(OUTPUTS)))
+    y = torch_statement(x, bn, residual, residual_bn)
+    if outputs == "float":
+        return y
+    return y.to(x.dtype) if outputs == "half" else (y, y.to(x.dtype))
+
+
+def _autocast_envelope_reason(x, bn, residual, residual_bn, outputs):
+    if outputs not in OUTPUTS:
+        return "outputs is %r, not one of %s" % (outputs, ", ".join(OUTPUTS))
+    if not torch.is_tensor(x) or x.dim() != 4:
+        return "x is not a (B, C, H, W) tensor"
+    dt = _autocast_dtype()
+    if dt is None:
+        return "autocast is not enabled on the device"
+    if x.dtype not in _HALF_CODES:
+        return "x is %s, not float16 or bfloat16" % x.dtype
+    if dt != x.dtype:
+        return "the autocast dtype is %s, x is %s" % (dt, x.dtype)
+    if not x.is_cuda:
+        return "x is not on a ROCm device"
+    if x.numel() == 0:
+        return "empty input"
+    if not x.is_contiguous():
+        return "x is not contiguous NCHW"
+    C = x.shape[1]
+    if x.shape[2] * x.shape[3] > 2 ** 31 - 1025:
+        return "plane of %d x %d" % (x.shape[2], x.shape[3])
+    r = _norm_reason(bn, C, x.device, "bn")
+    if r is not None:
+        return r
+    if residual is None:
+        if residual_bn is not None:
+            return "residual_bn without a residual"
+        return None
+    if outputs == "half":
+        return "the half output alone is served without a residual"
+    if not torch.is_tensor(residual) or residual.shape != x.shape:
+        return "residual does not have x's shape"
+    if residual.device != x.device:
+        return "residual is not on %s" % (x.device,)
+    if residual_bn is None:
+        if residual.dtype != torch.float32:
+            return "residual is %s without a residual_bn: an identity is float32" % residual.dtype
+    elif residual.dtype != x.dtype:
+        return "residual is %s with a residual_bn: a downsample convolution's output is %s" % (residual.dtype, x.dtype)
+    if not residual.is_contiguous():
+        return "residual is not contiguous NCHW"
+    if residual_bn is not None:
+        return _norm_reason(residual_bn, C, x.device, "residual_bn")
+    return None
+
+
+def autocast_fallback_reason(x, bn, residual=None, residual_bn=None, outputs="float"):
+    """why norm_relu_autocast(x, bn, residual, residual_bn, outputs) runs autocast_statement (None: the fused pass serves it).
+    Reads no device memory."""
+    least = AUTOCAST_AUTOGRAD_MIN_ELEMENTS.get("affine" if residual_bn is not None else outputs, 0)
+    return _speed_reason(_autocast_envelope_reason(x, bn, residual, residual_bn, outputs), least, x, residual)
+
+
+class _AutocastFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, r, r_scale, r_shift, outputs):
+        B, C, H, W = x.shape
+        y32 = torch.empty(x.shape, dtype=torch.float32, device=x.device) if outputs != "half" else None
+        y16 = torch.empty_like(x) if outputs != "float" else None
+        _call("ac_fwd", "halo_autocast_norm_relu_fwd", x.device, (x, scale, shift, r, r_scale, r_shift, y32, y16), _HALF_CODES[x.dtype], B, C, H * W)
+        if y32 is None:
+            ctx.save_for_backward(x, scale, shift)         # no y32 to read the gate off: pre is recomputed from x
+        else:
+            ctx.save_for_backward(y32, scale, r_scale)
+        ctx.outputs, ctx.half = outputs, x.dtype
+        ctx.set_materialize_grads(False)                   # an output nobody used arrives as None and is not read
+        return (y32, y16) if outputs == "both" else y32 if outputs == "float" else y16
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        g32, g16 = grads if ctx.outputs == "both" else (grads[0], None) if ctx.outputs == "float" else (None, grads[0])
+        want_x, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        if not (want_x or want_r) or (g32 is None and g16 is None):
+            return None, None, None, None, None, None, None
+        y32 = x = shift = r_scale = None
+        if ctx.outputs == "half":
+            x, scale, shift = ctx.saved_tensors
+            like = x
+        else:
+            y32, scale, r_scale = ctx.saved_tensors
+            like = y32
+        B, C, H, W = like.shape
+        g32 = None if g32 is None else g32.to(device=like.device, dtype=torch.float32).contiguous()
+        g16 = None if g16 is None else g16.to(device=like.device, dtype=ctx.half).contiguous()
+        gx = torch.empty(like.shape, dtype=ctx.half, device=like.device) if want_x else None
+        gr = torch.empty(like.shape, dtype=ctx.half if r_scale is not None else torch.float32, device=like.device) if want_r else None
+        _call("ac_bwd", "halo_autocast_norm_relu_bwd", like.device, (g32, g16, y32, x, scale, shift, r_scale if want_r else None, gx, gr),
+              _HALF_CODES[ctx.half], B, C, H * W)
+        return gx, None, None, gr, None, None, None
+
+
+def norm_relu_autocast(x, bn, residual=None, residual_bn=None, outputs="float"):
+    """norm_relu under torch.autocast, for the half x a convolution returns there: the stock chain's bits, and those of the cast
+    with which autocast would hand its result to the next convolution.
+
+        outputs="float" -> y32         relu(bn(x) [+ residual | + residual_bn(residual)]), float32 as the stock chain returns it
+        outputs="half"  -> y16         y32.to(x.dtype), for a result whose only reader is a convolution (a block's bn1 / bn2
+                                       positions); y32 is never written.  Without a residual only
+        outputs="both"  -> (y32, y16)  one autograd node with two outputs: a block output that a convolution reads (y16) and an
+                                       identity or anything else (y32)
+
+    residual is float32 of x's shape without a residual_bn (a block's identity), or of x's half dtype with one (the downsample
+    convolution's output).  Differentiable w.r.t. x and residual; x is not modified; the gradient of x is x's half dtype, that of
+    a float32 residual float32.  The backward is one pass: it reads the gradients that arrived (at y32, at y16 or at both, which
+    it adds as the engine would: one float32 add), computes only the gradients asked for, and launches nothing when none is.  It
+    keeps y32 and the scales.  outputs="half" has no y32, and y16 cannot stand in for the ReLU's gate -- a small positive y32 rounds
+    to a half zero, where the chain's gradient passes --, so that node keeps x, which the convolution behind it keeps anyway,
+    and its backward recomputes pre = fl(fl(float(x) * scale) + shift) from it.  Outside the served envelope
+    (autocast_fallback_reason) it returns autocast_statement(x, bn, residual, residual_bn, outputs)."""
+    if autocast_fallback_reason(x, bn, residual, residual_bn, outputs) is not None:
+        return autocast_statement(x, bn, residual, residual_bn, outputs)
+    return _AutocastFn.apply(*_tail_operands(x, bn, residual, residual_bn), outputs)
+
+
 __all__ = ["norm_relu", "norm_relu_fork", "fork_fallback_reason", "torch_statement", "fallback_reason", "cached_scale_shift", "forget", "norm_relu_dropout2d",
            "dropout_statement", "dropout_fallback_reason", "norm_relu_dropout2d_pair", "pair_statement", "pair_fallback_reason",
-           "norm_relu_maxpool", "pool_statement", "pool_fallback_reason"]
+           "norm_relu_maxpool", "pool_statement", "pool_fallback_reason", "norm_relu_autocast", "autocast_statement", "autocast_fallback_reason"]

@@ -16,7 +16,8 @@
  *   - scratch comes from the caller: size it with the matching *_workspace_bytes()
  *   - return 0 on success, <0 on error (HALO_E_*); halo_last_error() gives the message of the
  *     calling thread's last failure
- *   - dtype codes: HALO_F32 = 0, HALO_F64 = 1; integer maps (labels, predictions): HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4
+ *   - dtype codes: HALO_F32 = 0, HALO_F64 = 1; integer maps (labels, predictions): HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4;
+ *     half operands of the autocast passes: HALO_F16 = 5, HALO_BF16 = 6
  */
 #ifndef HALO_HIP_H
 #define HALO_HIP_H
@@ -30,7 +31,7 @@ extern "C" {
 
 #define HALO_ABI_VERSION 13
 
-enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4 };
+enum { HALO_F32 = 0, HALO_F64 = 1, HALO_I64 = 2, HALO_I32 = 3, HALO_U8 = 4, HALO_F16 = 5, HALO_BF16 = 6 };
 
 enum { HALO_OK = 0, HALO_E_ARG = -1, HALO_E_UNSUPPORTED = -2, HALO_E_WORKSPACE = -3, HALO_E_LAUNCH = -4 };
 
@@ -528,6 +529,27 @@ int halo_affine_relu_bwd(const float *g, const float *y, const float *scale, con
  *  and limits are those of the single-gradient entry; a NULL g_a or g_b is HALO_E_ARG. */
 int halo_fork_affine_relu_bwd(const float *g_a, const float *g_b, const float *y, const float *scale, const float *r_scale, float *g_x,
                               float *g_r, int64_t B, int64_t C, int64_t HW, void *stream);
+
+/* ---- the same chain under torch.autocast (halo_norm_autocast.hip, halo_amd/norm.py: norm_relu_autocast) ----
+ *  The convolution in front returns half, the stock statements promote to float32, autocast rounds the result back to half for
+ *  the next convolution.  half_dtype = HALO_F16 | HALO_BF16 is the element type of every half operand of a call: x, y16, g16, g_x
+ *  always; r and g_r when r_scale is given (the downsample convolution's output, its norm folded in).  Without r_scale r and g_r are
+ *  float32 (the block's identity).  y32, g32 float32; all (B, C, HW) dense NCHW planes; scale, shift, r_scale, r_shift (C) f32.
+ *    pre = fl(fl(float(x) scale[c]) + shift[c]);  id = r32  or  fl(fl(float(r16) r_scale[c]) + r_shift[c])
+ *    s = pre  or  fl(pre + id);  y32 = s <= 0 ? 0 : s (a NaN stays a NaN);  y16 = rne_half(y32)
+ *    g = g32,  float(g16)  or  fl(g32 + float(g16));  gp = s <= 0 ? 0 : g (a NaN s lets g through)
+ *    g_x = rne_half(fl(gp scale[c]));  g_r = gp  or  rne_half(fl(gp r_scale[c]))
+ *  half -> float is exact; float -> half rounds to nearest even, overflows to +-inf, keeps a NaN a NaN (payload not specified).
+ *  fwd: a NULL y32 or y16 is not written, one of them must be given.  bwd: a NULL g32 or g16 is not read, one of them must be
+ *  given; the gate s <= 0 is read off y32, or off pre recomputed from x, scale and shift -- exactly one of y32 and x is given, and
+ *  x only for a pass without a residual (g_r NULL): y16 cannot stand in for it, a small positive y32 rounds to a half zero.  A
+ *  NULL g_x or g_r is neither computed nor written.  Outputs must not overlap inputs.  HW % 8 == 0 with every operand 16-byte
+ *  aligned runs 16-byte accesses, anything else one element per lane: same statements, same bits.  HALO_E_ARG: an empty shape, a
+ *  missing or contradictory pointer, another half_dtype; HALO_E_UNSUPPORTED: HW above 2^31 - 1025 or more than 2^31 - 1 workgroups. */
+int halo_autocast_norm_relu_fwd(const void *x, const float *scale, const float *shift, const void *r, const float *r_scale,
+                                const float *r_shift, float *y32, void *y16, int half_dtype, int64_t B, int64_t C, int64_t HW, void *stream);
+int halo_autocast_norm_relu_bwd(const float *g32, const void *g16, const float *y32, const void *x, const float *scale, const float *shift,
+                                const float *r_scale, void *g_x, void *g_r, int half_dtype, int64_t B, int64_t C, int64_t HW, void *stream);
 
 /* ---- frozen norm + ReLU + Dropout2d: the pointwise tail of a separable block and the dropout behind it (halo_amd/norm.py) ----
  *  x, y, g, g_x (B, C, HW) f32 dense NCHW planes; scale, shift (C) f32; mask (B, C) f32: the multiplier of plane (b, c), 0 or
