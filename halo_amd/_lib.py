@@ -149,6 +149,8 @@ SIGNATURES = {
     "halo_score_range": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp]),
     "halo_greedy_select": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _sz, _int, _vp, _vp, _vp]),
+    "halo_select_first_tranche": (_i64, [_i64, _i64, _i64, _i64]),
+    "halo_select_stats": (_int, [_vp, _sz, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
 }
 
 # must equal HALO_ABI_VERSION of include/halo_hip.h; bumped whenever an exported signature changes, so a stale

@@ -22,7 +22,7 @@ from .floating_region import FloatingRegionScore, new_score_range, score_maps, s
 
 
 def greedy_select(score, n_regions, active_radius, mask_radius, active, selected, active_mask, ground_truth,
-                  return_picks=True, method=None, out=None, score_range=None, handover=None):
+                  return_picks=True, method=None, out=None, score_range=None, handover=None, stats=None):
     """Batched device-side selection.  score (B,H,W) f32|f64, active/selected (B,H,W) bool,
     active_mask/ground_truth (B,H,W) int64 -- all on one ROCm device, all mutated in place.
     Returns (picks (B,n,3) float64 rows (h, w, value), n_picked (B,) int32) or None.
@@ -34,7 +34,10 @@ def greedy_select(score, n_regions, active_radius, mask_radius, active, selected
     pass over the map for the value range (the records only have to bound the values: the picks do not depend on them).
     handover: optional (B,2) int32 device tensor that receives, per image, {reason, picks made by the sweep} -- reason 0
     (_lib.SWEEP_REASONS[0]) = the value-binned sweep finished the image, anything else = the serial kernel continued it from that
-    pick on.  A cost counter only: results never depend on which kernel made a pick."""
+    pick on.  A cost counter only: results never depend on which kernel made a pick.
+    stats: optional (B,3) int32 device tensor that receives, per image, {candidates the sweep placed, candidates in the chunks it
+    processed, sweep rounds run}: 2 rounds = the first tranche of candidates (halo_select_first_tranche) ran out and the rest of
+    the proven bound was placed and swept as well; zeros where the sweep did not run.  Cost counters, like handover."""
     dev = _lib.require_device(score, active, selected, active_mask, ground_truth)
     B, H, W = score.shape
     for t in (score, active, selected, active_mask, ground_truth):
@@ -53,9 +56,13 @@ def greedy_select(score, n_regions, active_radius, mask_radius, active, selected
         n_picked = torch.zeros((B,), dtype=torch.int32, device=dev)
     if handover is not None:
         assert handover.shape == (B, 2) and handover.dtype == torch.int32 and handover.is_contiguous() and handover.device == dev
+    if stats is not None:
+        assert stats.shape == (B, 3) and stats.dtype == torch.int32 and stats.is_contiguous() and stats.device == dev
     if n == 0 or B == 0:
         if handover is not None:
             handover.zero_()
+        if stats is not None:
+            stats.zero_()
         return (picks[:, :0], n_picked) if return_picks else None
     L = _lib.lib()
     name = method or os.environ.get("HALO_SELECT", "auto")
@@ -71,6 +78,12 @@ def greedy_select(score, n_regions, active_radius, mask_radius, active, selected
                               _lib.ptr(ground_truth), _lib.ptr(picks), _lib.ptr(n_picked), _lib.ptr(ws), ws.numel(),
                               method, _lib.ptr(score_range), _lib.ptr(handover), _lib.stream_ptr(dev))
     _lib.check(rc, "halo_greedy_select")
+    if stats is not None:
+        if method == _lib.SELECT["serial"]:
+            stats.zero_()
+        else:
+            _lib.check(L.halo_select_stats(_lib.ptr(ws), ws.numel(), B, H, W, n, int(mask_radius), _lib.ptr(stats), _lib.stream_ptr(dev)),
+                       "halo_select_stats")
     return (picks, n_picked) if return_picks else None
 
 

@@ -282,6 +282,24 @@ extern "C" size_t halo_select_workspace_bytes(int64_t B, int64_t H, int64_t W, i
     return p.ok ? p.total_bytes + 256 : 256;
 }
 
+extern "C" int64_t halo_select_first_tranche(int64_t H, int64_t W, int64_t n_regions, int64_t mask_radius)
+{
+    if (H <= 0 || W <= 0 || n_regions <= 0 || mask_radius < 0) return 0;
+    if (n_regions > H * W) n_regions = H * W;
+    const unsigned long long hw = (unsigned long long)H * W, win = (unsigned long long)(2 * mask_radius + 1) * (2 * mask_radius + 1);
+    const unsigned long long kneed = win * (unsigned long long)n_regions < hw ? win * (unsigned long long)n_regions : hw;
+    return (int64_t)tranche_first(kneed, (unsigned long long)n_regions);
+}
+
+extern "C" int halo_select_stats(const void *workspace, size_t workspace_bytes, int64_t B, int64_t H, int64_t W, int64_t n_regions,
+                                 int64_t mask_radius, int32_t *stats, void *stream)
+{
+    if (!stats || B <= 0 || H <= 0 || W <= 0 || n_regions < 0 || mask_radius < 0) return fail(HALO_E_ARG, "halo_select_stats: null/empty argument");
+    if (n_regions > H * W) n_regions = H * W;
+    const BinPlan p = binned_plan(B, H, W, n_regions, 0, mask_radius);
+    return binned_stats(B, p, workspace, workspace_bytes, stats, (hipStream_t)stream);
+}
+
 template <typename T, int A, int B_, int EPT>
 static int launch_serial(const SelGeom &g, size_t lds, dim3 grid, hipStream_t st, void *score, int n_regions, int arad, int mrad,
                          uint8_t *active, uint8_t *selected, int64_t *active_mask, const int64_t *gt, double *picks,

@@ -17,12 +17,14 @@
 //   k_sel_range    min / max of the finite values, count of pickable pixels
 //   k_sel_hist1    2048 equal-width coarse bins over [min, max]                      (LDS histograms)
 //   k_sel_scan1    threshold bin t1 (top-K), every coarse bin split into count/target equal sub-bins
-//   k_sel_place    pixels >= t1 -> a slot of their fine bin (one returned atomic per candidate; bins have BIN_CAP slots
-//                  and are numbered in descending value order) -- round 2 went through a staging list, a fine histogram,
-//                  a prefix scan and a scatter pass
+//   k_sel_place    pixels >= t1a (the first tranche, halo_select_plan.hpp) -> a slot of their fine bin (one returned atomic
+//                  per candidate; bins have BIN_CAP slots and are numbered in descending value order) -- round 2 went
+//                  through a staging list, a fine histogram, a prefix scan and a scatter pass
 //   k_sel_sweep    ONE workgroup per image walks the bins: filter a bin's candidates against the
 //                  pick grid (4 waves, one candidate per lane), then wave 0 takes the survivors
 //                  in exact (value, w, h) order with a register-resident arg-max loop
+//   (k_sel_place, k_sel_full_extrema and k_sel_sweep once more for the bins [t1, t1a): they return at once unless the image's
+//                  first tranche ran out before n_regions picks)
 //   k_sel_apply    one wave per pick writes its (h, w, value) row of the pick table and its windows
 //                  (score = -inf, active, selected, active_mask)
 // Order inside a bin never matters (the resolve step is an exact arg-max over the bin's survivors),
@@ -164,7 +166,7 @@ __global__ void __launch_bounds__(256) k_sel_hist1(const T *__restrict__ score, 
 // range downwards, cbase[j] = sum of m over the bins above j.
 __global__ void __launch_bounds__(256) k_sel_scan1(BinWs ws, BinGeom g)
 {
-    __shared__ unsigned sc_c[256], sc_m[256], s_t1;
+    __shared__ unsigned sc_c[256], sc_m[256], s_t1, s_t1a, s_nfa;
     const int b = blockIdx.x, tid = threadIdx.x;
     SelHdr *hdr = ws.hdr + b;
     const ValRange r = sel_range(ws.rng[b]);
@@ -183,7 +185,7 @@ __global__ void __launch_bounds__(256) k_sel_scan1(BinWs ws, BinGeom g)
     }
     sc_c[tid] = tc;
     sc_m[tid] = tm;
-    if (tid == 0) s_t1 = 0;
+    if (tid == 0) { s_t1 = 0; s_t1a = 0; s_nfa = 0; }
     __syncthreads();
     // inclusive suffix scan over the 256 per-thread totals (Hillis-Steele)
     for (int d = 1; d < 256; d <<= 1) {
@@ -207,11 +209,24 @@ __global__ void __launch_bounds__(256) k_sel_scan1(BinWs ws, BinGeom g)
     for (int i = 0; i < 8; ++i)
         if (S[i] >= g.kneed) mine = tid * 8 + i;
     if (mine > 0) atomicMax(&s_t1, (unsigned)mine);
+    // the first tranche: the same rule with kfirst <= kneed, so t1a >= t1
+    int mine_a = -1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        if (S[i] >= g.kfirst) mine_a = tid * 8 + i;
+    if (mine_a > 0) atomicMax(&s_t1a, (unsigned)mine_a);
     unsigned *cb = ws.cbase + (size_t)b * NB1, *cmm = ws.cm + (size_t)b * NB1;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { cb[tid * 8 + i] = M[i]; cmm[tid * 8 + i] = m[i]; }
     __syncthreads();
     unsigned t1 = s_t1;
+    const unsigned t1a_raw = s_t1a;
+    if ((int)(t1a_raw >> 3) == tid) {             // fine bins of the coarse bins >= t1a
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (q == (int)(t1a_raw & 7)) s_nfa = M[q] + m[q];
+    }
+    __syncthreads();
     // the thread owning bin t1 decides about truncation and publishes the layout
     if ((int)(t1 >> 3) == tid) {
         const int i = t1 & 7;
@@ -227,6 +242,10 @@ __global__ void __launch_bounds__(256) k_sel_scan1(BinWs ws, BinGeom g)
         hdr->t1 = t1;
         hdr->truncated = trunc;
         hdr->nf = nf;
+        // a dropped threshold bin takes the first tranche's edge with it (t1a == t1 before: then one tranche, as ever)
+        const bool one = !r.ok || t1a_raw < t1;
+        hdr->t1a = one ? t1 : t1a_raw;
+        hdr->nf_a = one ? nf : s_nfa;
     }
     __syncthreads();
     if (ext && tid == 0) ws.rng[b].flags &= ~(unsigned)SEL_F_HIST;      // consumed
@@ -235,17 +254,20 @@ __global__ void __launch_bounds__(256) k_sel_scan1(BinWs ws, BinGeom g)
 // ------------------------------------------------------------------ candidates -> their fine bins, in one pass
 // Round 3: a candidate goes straight to a slot of its fine bin -- one returned atomic on the bin's counter, two stores --
 // instead of staging list -> fine histogram -> prefix scan -> scatter (round 2: two atomics and a 16-byte round trip per
-// candidate, three launches).  Bins have BIN_CAP slots; a candidate that finds its bin full marks the image SEL_F_OVERFLOW and
-// the sweep hands it over untouched.
+// candidate, three launches).  Bins have BIN_CAP slots; a candidate that finds its bin full is dropped and marks the image
+// SEL_F_OVERFLOW: k_sel_full_extrema then records the key range of the full bins, and the sweep walks such a bin through the map
+// itself when it reaches it (plateau_scan).  `round`: which tranche of coarse bins this launch places.
 template <typename T>
-__global__ void __launch_bounds__(256) k_sel_place(const T *__restrict__ score, BinWs ws, BinGeom g)
+__global__ void __launch_bounds__(256) k_sel_place(const T *__restrict__ score, BinWs ws, BinGeom g, int round)
 {
     __shared__ unsigned s_base[NB1], s_m[NB1];
     const int b = blockIdx.y, tid = threadIdx.x;
     SelHdr *hdr = ws.hdr + b;
+    if (round != 0 && hdr->status != SEL_MORE) return;      // round B: only for an image whose first tranche ran out
     const ValRange r = sel_range(ws.rng[b]);
-    const unsigned t1 = hdr->t1;
-    if (!r.ok || t1 >= NB1) return;
+    // coarse bins [t1, t_end) of this round: A places the first tranche [t1a, NB1), B the rest of the top kneed, [t1, t1a)
+    const unsigned t1 = round == 0 ? hdr->t1a : hdr->t1, t_end = round == 0 ? (unsigned)NB1 : hdr->t1a;
+    if (!r.ok || t1 >= t_end) return;
     for (int j = tid; j < NB1; j += 256) { s_base[j] = ws.cbase[(size_t)b * NB1 + j]; s_m[j] = ws.cm[(size_t)b * NB1 + j]; }
     __syncthreads();
     const T *sc = score + (size_t)b * g.H * g.W;
@@ -272,7 +294,7 @@ __global__ void __launch_bounds__(256) k_sel_place(const T *__restrict__ score, 
                 cand[u] = k[u] < KEY_POS_INF && k[u] != KEY_NEG_INF;
                 double t = 0.0;
                 const int j = cand[u] ? coarse_bin(v[u], r, t) : 0;
-                cand[u] = cand[u] && (unsigned)j >= t1;
+                cand[u] = cand[u] && (unsigned)j - t1 < t_end - t1;
                 f[u] = 0;
                 if (cand[u]) {
                     const unsigned mj = s_m[j];
@@ -331,15 +353,16 @@ __global__ void __launch_bounds__(256) k_sel_place(const T *__restrict__ score, 
 // k_sel_place itself, with one slot atomic per wave for plateaus: 48 -> 58-70 registers, one wave per SIMD instead of two beside
 // the feature kernel, 850 -> 1340 us per 16 ordinary images.)
 template <typename T>
-__global__ void __launch_bounds__(256) k_sel_full_extrema(const T *__restrict__ score, BinWs ws, BinGeom g)
+__global__ void __launch_bounds__(256) k_sel_full_extrema(const T *__restrict__ score, BinWs ws, BinGeom g, int round)
 {
     __shared__ unsigned s_base[NB1], s_m[NB1];
     const int b = blockIdx.y, tid = threadIdx.x;
     const SelHdr *hdr = ws.hdr + b;
     if (!(hdr->flags & SEL_F_OVERFLOW)) return;
+    if (round != 0 && hdr->status != SEL_MORE) return;
     const ValRange r = sel_range(ws.rng[b]);
-    const unsigned t1 = hdr->t1;
-    if (!r.ok || t1 >= NB1) return;
+    const unsigned t1 = round == 0 ? hdr->t1a : hdr->t1, t_end = round == 0 ? (unsigned)NB1 : hdr->t1a;      // as k_sel_place
+    if (!r.ok || t1 >= t_end) return;
     for (int j = tid; j < NB1; j += 256) { s_base[j] = ws.cbase[(size_t)b * NB1 + j]; s_m[j] = ws.cm[(size_t)b * NB1 + j]; }
     __syncthreads();
     const T *sc = score + (size_t)b * g.H * g.W;
@@ -353,7 +376,7 @@ __global__ void __launch_bounds__(256) k_sel_full_extrema(const T *__restrict__ 
             bool cand = k < KEY_POS_INF && k != KEY_NEG_INF;
             double t = 0.0;
             const int j = cand ? coarse_bin(v, r, t) : 0;
-            cand = cand && (unsigned)j >= t1;
+            cand = cand && (unsigned)j - t1 < t_end - t1;
             unsigned f = 0;
             if (cand) {
                 const unsigned mj = s_m[j];
@@ -497,8 +520,13 @@ __device__ __forceinline__ int resolve_bin_parallel(const unsigned long long *sk
 // (at most 96 registers: k_feat_reduce's cap leaves 512 - 4 x 104 = 96 per SIMD free, and a sweep workgroup that needs more waits
 // for a CU to drain -- with plateau_scan inlined the compiler took 97, and 16 selections beside the streaming kernel went from 2.5
 // to 3.0 ms)
+// Two launches per call.  Round A (round = 0) walks the first tranche, the fine bins [0, nf_a): reaching n_regions, or any hand-over,
+// ends the image as ever; when the candidates run out and a second tranche exists (t1a > t1) the image is left SEL_MORE with its picks in
+// plist.  Round B (round = 1) returns at once unless the image is SEL_MORE; otherwise it rebuilds the pick grid from plist[0, np) and
+// walks [nf_a, nf) -- k_sel_place filled those bins between the two launches -- and ends by the same rules.  Nothing is shared inside a
+// launch: what round A hands over lies in the header (cleared per call, written by round A) and in plist.
 __global__ void __launch_bounds__(SW_TPB, 5) k_sel_sweep(BinWs ws, BinGeom g, int *__restrict__ n_picked, const void *__restrict__ score_maps,
-                                                      int score_f64)
+                                                      int score_f64, int round)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *grid = smem;                                               // pick grid, one byte per cell (+ border)
@@ -511,7 +539,8 @@ __global__ void __launch_bounds__(SW_TPB, 5) k_sel_sweep(BinWs ws, BinGeom g, in
     __builtin_amdgcn_s_setprio(3);     // a short serial chain beside bandwidth-bound kernels: issue ahead of them
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     SelHdr *hdr = ws.hdr + b;
-    const unsigned nf = hdr->nf;
+    if (round != 0 && hdr->status != SEL_MORE) return;
+    const unsigned nf = round == 0 ? hdr->nf_a : hdr->nf;           // one past the last fine bin of this round
     const bool truncated = hdr->truncated != 0;
     const unsigned *fcnt = ws.fcur + (size_t)b * g.nfmax;
     const unsigned long long *ckey = ws.ckey + (size_t)b * g.nfmax * BIN_CAP;
@@ -526,6 +555,17 @@ __global__ void __launch_bounds__(SW_TPB, 5) k_sel_sweep(BinWs ws, BinGeom g, in
     __syncthreads();
 
     int np = 0;                                  // maintained by wave 0
+    if (round != 0) {                            // the picks of round A back into the grid
+        np = hdr->np;
+        for (int i = tid; i < np; i += SW_TPB) {
+            const unsigned pos = plist[i];
+            const int px = (int)(pos >> 16), py = (int)(pos & 0xffffu);
+            const int pcx = (int)__umulhi((unsigned)px, g.cmul), pcy = (int)__umulhi((unsigned)py, g.cmul);
+            grid[(pcy + 1) * g.gstride + pcx + 1] = (unsigned char)(1 + (((py - pcy * g.cs) << 4) | (px - pcx * g.cs)));
+        }
+        __syncthreads();
+    }
+    unsigned consumed = 0;                       // counter: candidates in the chunks processed
     int fin = 0;                                 // 0 running, 1 done, 2 bail
     int why = HALO_SWEEP_DONE;                   // reason of a hand-over (reported through ws.handover)
     const int r = g.mrad, cs = g.cs;
@@ -541,7 +581,7 @@ __global__ void __launch_bounds__(SW_TPB, 5) k_sel_sweep(BinWs ws, BinGeom g, in
     // halves the number of filter / resolve rounds (two barriers and a serial resolve each) for the same candidates.
     struct Chunk { unsigned start[SW_MB], cnt[SW_MB], total; bool last, valid, plateau; unsigned pbin; };
     unsigned fw0 = 0, fwn = 0;                   // fwin holds the candidate counts of bins fw0 .. fw0 + fwn - 1
-    unsigned it_f = 0;                           // next bin to look at
+    unsigned it_f = round == 0 ? 0u : hdr->nf_a; // next bin to look at
     // A bin that ran out of slots (more than BIN_CAP candidates in one sub-slice of the value range: a plateau of ties) becomes a
     // chunk of its own kind, in its place in the stream: when the walk REACHES it -- everything above it has been swept -- the
     // plateau is walked through the map itself if all its candidates carry one key (plateau_scan below), and handed to the serial
@@ -745,6 +785,7 @@ __global__ void __launch_bounds__(SW_TPB, 5) k_sel_sweep(BinWs ws, BinGeom g, in
     // one chunk: filter against the pick grid, survivors -> LDS list; at the end of a bin wave 0 resolves the survivors
     auto step = [&](const Chunk &c, const Regs &d) {
         if (c.plateau) { plateau_scan(c.pbin); return; }
+        consumed += c.total;
         push((unsigned)tid < c.total && grid_alive(d.pos), d.key, d.pos);
         if (!c.last) return;
         resolve_listed();
@@ -765,21 +806,27 @@ __global__ void __launch_bounds__(SW_TPB, 5) k_sel_sweep(BinWs ws, BinGeom g, in
         step(c2, d2);
         c2 = next_chunk(); issue(c2, d2);
     }
-#ifdef HALO_SWEEP_STAMPS
-    if (tid == 0) {      // diagnostic build only: phase cycle sums of wave 0 into the header's padding words
-        hdr->pad[0] = (unsigned)(t_f >> 4); hdr->pad[1] = (unsigned)(t_a >> 4); hdr->pad[2] = (unsigned)(t_r >> 4); hdr->pad[3] = (unsigned)(t_b >> 4);
-        hdr->nvalid = (unsigned)nb; hdr->ncand = (unsigned)t_surv; hdr->flags = (unsigned)t_smax;
-    }
-#endif
     if (tid == 0) {
-        if (fin == 0) {                          // candidates exhausted: final unless the threshold bin was dropped
-            fin = truncated ? 2 : 1;
-            if (truncated) why = hdr->t1 >= (unsigned)NB1 ? HALO_SWEEP_BAD_VALUES : HALO_SWEEP_EXHAUSTED;
-        }
-        if (ws.handover) { ws.handover[2 * b] = fin == 1 ? HALO_SWEEP_DONE : why; ws.handover[2 * b + 1] = np; }
+        hdr->consumed = (round == 0 ? 0u : hdr->consumed) + consumed;
+        hdr->rounds = (unsigned)round + 1u;
         hdr->np = np;
-        hdr->status = fin == 1 ? SEL_DONE : SEL_BAIL;
-        if (fin == 1 && n_picked) n_picked[b] = np;
+        if (fin == 0 && round == 0 && hdr->t1a != hdr->t1) hdr->status = SEL_MORE;      // the first tranche ran out: round B goes on
+        else {
+            if (fin == 0) {                      // candidates exhausted: final unless the threshold bin was dropped
+                fin = truncated ? 2 : 1;
+                if (truncated) why = hdr->t1 >= (unsigned)NB1 ? HALO_SWEEP_BAD_VALUES : HALO_SWEEP_EXHAUSTED;
+            }
+            if (ws.handover) { ws.handover[2 * b] = fin == 1 ? HALO_SWEEP_DONE : why; ws.handover[2 * b + 1] = np; }
+            hdr->status = fin == 1 ? SEL_DONE : SEL_BAIL;
+            if (fin == 1 && n_picked) n_picked[b] = np;
+#ifdef HALO_SWEEP_STAMPS
+            // diagnostic build only: the phase cycle sums of wave 0 in the round that ENDED the image (round A on ordinary maps; a
+            // later launch of the call returns at once for it) over the header's last four words and three it no longer needs --
+            // tools/sweep_stamps.py reads them there; the counters of halo_select_stats are not valid in such a build
+            hdr->t1a = (unsigned)(t_f >> 4); hdr->nf_a = (unsigned)(t_a >> 4); hdr->consumed = (unsigned)(t_r >> 4); hdr->rounds = (unsigned)(t_b >> 4);
+            hdr->nvalid = (unsigned)nb; hdr->ncand = (unsigned)t_surv; hdr->flags = (unsigned)t_smax;
+#endif
+        }
     }
 }
 
@@ -839,6 +886,33 @@ __global__ void __launch_bounds__(256) k_sel_apply(T *__restrict__ score, unsign
     }
 }
 
+// ------------------------------------------------------------------ counters of the last call
+// One workgroup per image: {candidates placed (what the fine bins of both tranches hold), candidates in the chunks the sweep
+// processed, sweep rounds run}.  hdr == NULL: the sweep does not serve the geometry, zeros.
+__global__ void __launch_bounds__(256) k_sel_stats(BinWs ws, BinGeom g, int *__restrict__ stats)
+{
+    __shared__ unsigned s_sum[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (!ws.hdr) {
+        if (tid < 3) stats[3 * b + tid] = 0;
+        return;
+    }
+    const SelHdr *hdr = ws.hdr + b;
+    const unsigned nf = hdr->rounds ? hdr->nf : 0u;
+    const unsigned *fcnt = ws.fcur + (size_t)b * g.nfmax;
+    unsigned n = 0;
+    for (unsigned f = tid; f < nf; f += 256) n += fcnt[f] < (unsigned)BIN_CAP ? fcnt[f] : (unsigned)BIN_CAP;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if ((tid & 63) == 0) s_sum[tid >> 6] = n;
+    __syncthreads();
+    if (tid == 0) {
+        stats[3 * b] = (int)(s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
+        stats[3 * b + 1] = (int)hdr->consumed;
+        stats[3 * b + 2] = (int)hdr->rounds;
+    }
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -866,6 +940,7 @@ BinPlan binned_plan(int64_t B, int64_t H, int64_t W, int64_t n_regions, int64_t 
     unsigned long long cap = 2 * kneed < 65536 ? 65536 : 2 * kneed;
     if (cap > hw) cap = hw;
     g.kneed = (unsigned)kneed;
+    g.kfirst = (unsigned)tranche_first(kneed, (unsigned long long)n_regions);
     g.captot = (unsigned)cap;
     g.target = (unsigned)(BIN_CAP / 2);       // expected candidates per fine bin: bins are Poisson-filled, keep 2x headroom
     g.nfmax = (unsigned)(cap / g.target + NB1 + 1);
@@ -910,6 +985,7 @@ int binned_select(void *score, int dtype, int64_t B, const BinPlan &p, uint8_t *
     char *base = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     if ((size_t)(base - (char *)workspace) + p.total_bytes - 256 > workspace_bytes) return fail(HALO_E_WORKSPACE, "halo_greedy_select: workspace too small");
     BinWs ws;
+    memset(&ws, 0, sizeof(ws));
     ws.hdr = (SelHdr *)(base + p.off_hdr);
     ws.rng = score_range ? (SelHdr *)score_range : ws.hdr;            // the scorer already knows the range: no pass over the map
     ws.rng_hist = score_range ? (const unsigned *)((const char *)score_range + range_hist_offset(B)) : nullptr;
@@ -945,17 +1021,25 @@ int binned_select(void *score, int dtype, int64_t B, const BinPlan &p, uint8_t *
         hipLaunchKernelGGL(k_sel_hist1<float>, dim3(gx, (unsigned)B), blk, 0, st, (const float *)score, hw, ws);
     }
     hipLaunchKernelGGL(k_sel_scan1, dim3((unsigned)B), blk, 0, st, ws, g);
-    if (dtype == HALO_F64) hipLaunchKernelGGL(k_sel_place<double>, dim3(gy, (unsigned)B), blk, 0, st, (const double *)score, ws, g);
-    else hipLaunchKernelGGL(k_sel_place<float>, dim3(gy, (unsigned)B), blk, 0, st, (const float *)score, ws, g);
-    {   // rare: the extrema of bins that ran out of slots (returns at once unless k_sel_place flagged the image)
-        const dim3 ge((unsigned)(g.H < 64 ? g.H : 64), (unsigned)B);
-        if (dtype == HALO_F64) hipLaunchKernelGGL(k_sel_full_extrema<double>, ge, blk, 0, st, (const double *)score, ws, g);
-        else hipLaunchKernelGGL(k_sel_full_extrema<float>, ge, blk, 0, st, (const float *)score, ws, g);
-    }
     static LdsLimitSeen seen;      // the pick grid may need more than the default 64 KiB of dynamic LDS
     if (!raise_lds_limit(seen, (const void *)k_sel_sweep, 160 * 1024))
         return fail(HALO_E_LAUNCH, "halo_greedy_select: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL(k_sel_sweep, dim3((unsigned)B), dim3(SW_TPB), p.lds_bytes, st, ws, g, n_picked, (const void *)score, dtype == HALO_F64 ? 1 : 0);
+    // Round A: the first tranche (the top kfirst values).  Round B: the rest of the top kneed, for the images round A left SEL_MORE --
+    // launched always (nothing on the host knows), its workgroups return at once for every other image; few images ever need it,
+    // so its passes over the map get a quarter of round A's workgroups.
+    for (int round = 0; round < 2; ++round) {
+        const unsigned gp = round == 0 ? gy : (gy + 3) / 4;
+        if (dtype == HALO_F64) hipLaunchKernelGGL(k_sel_place<double>, dim3(gp, (unsigned)B), blk, 0, st, (const double *)score, ws, g, round);
+        else hipLaunchKernelGGL(k_sel_place<float>, dim3(gp, (unsigned)B), blk, 0, st, (const float *)score, ws, g, round);
+        {   // rare: the extrema of bins that ran out of slots (returns at once unless k_sel_place flagged the image)
+            const unsigned gh = (unsigned)(g.H < 64 ? g.H : 64);
+            const dim3 ge(round == 0 ? gh : (gh + 3) / 4, (unsigned)B);
+            if (dtype == HALO_F64) hipLaunchKernelGGL(k_sel_full_extrema<double>, ge, blk, 0, st, (const double *)score, ws, g, round);
+            else hipLaunchKernelGGL(k_sel_full_extrema<float>, ge, blk, 0, st, (const float *)score, ws, g, round);
+        }
+        hipLaunchKernelGGL(k_sel_sweep, dim3((unsigned)B), dim3(SW_TPB), p.lds_bytes, st, ws, g, n_picked, (const void *)score,
+                           dtype == HALO_F64 ? 1 : 0, round);
+    }
     const dim3 ga((unsigned)(cdiv(g.n_regions, 4) < APPLY_WGS ? cdiv(g.n_regions, 4) : APPLY_WGS), (unsigned)B);
     if (dtype == HALO_F64)
         hipLaunchKernelGGL(k_sel_apply<double>, ga, blk, 0, st, (double *)score, active, selected, (long long *)active_mask, (const long long *)gt, picks, ws, g);
@@ -963,6 +1047,21 @@ int binned_select(void *score, int dtype, int64_t B, const BinPlan &p, uint8_t *
         hipLaunchKernelGGL(k_sel_apply<float>, ga, blk, 0, st, (float *)score, active, selected, (long long *)active_mask, (const long long *)gt, picks, ws, g);
     *hdr_out = ws.hdr;
     return check_launch("halo_greedy_select (binned)");
+}
+
+int binned_stats(int64_t B, const BinPlan &p, const void *workspace, size_t workspace_bytes, int32_t *stats, hipStream_t st)
+{
+    BinWs ws;
+    memset(&ws, 0, sizeof(ws));
+    if (p.ok) {
+        if (!workspace || workspace_bytes < p.total_bytes) return fail(HALO_E_WORKSPACE, "halo_select_stats: workspace too small");
+        char *base = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+        if ((size_t)(base - (char *)workspace) + p.total_bytes - 256 > workspace_bytes) return fail(HALO_E_WORKSPACE, "halo_select_stats: workspace too small");
+        ws.hdr = (SelHdr *)(base + p.off_hdr);
+        ws.fcur = (unsigned *)(base + p.off_fcur);
+    }
+    hipLaunchKernelGGL(k_sel_stats, dim3((unsigned)B), dim3(256), 0, st, ws, p.g, stats);
+    return check_launch("halo_select_stats");
 }
 
 }  // namespace halo

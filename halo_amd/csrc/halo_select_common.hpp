@@ -83,12 +83,16 @@ struct SelHdr {
     unsigned nf;                   // fine bins in use
     unsigned t1;                   // first coarse bin that contributes candidates
     unsigned truncated;            // 1: the threshold bin was dropped (staging capacity) -> exhaustion is not final
-    int status;                    // SEL_RUN / SEL_DONE / SEL_BAIL
+    int status;                    // SEL_RUN / SEL_DONE / SEL_BAIL (SEL_MORE only between the sweep's two rounds)
     int np;                        // picks made so far
-    unsigned pad[4];
+    unsigned t1a;                  // first coarse bin of the first tranche (>= t1): round A places and sweeps the bins >= t1a
+    unsigned nf_a;                 // fine bins of the first tranche: round A walks [0, nf_a), round B [nf_a, nf)
+    unsigned consumed;             // counter: candidates in the chunks the sweep processed (both rounds)
+    unsigned rounds;               // counter: sweep rounds that worked on the image (0: the sweep did not run)
 };
 static_assert(sizeof(SelHdr) == 64, "SelHdr is 64 bytes");
-enum { SEL_RUN = 0, SEL_DONE = 1, SEL_BAIL = 2 };
+enum { SEL_RUN = 0, SEL_DONE = 1, SEL_BAIL = 2,
+       SEL_MORE = 3 };             // internal, between the two rounds of one call: the first tranche ran out before n_regions picks
 enum { SEL_F_BAD = 1,              // NaN or +inf present: the value range cannot be binned
        SEL_F_OVERFLOW = 2,         // a fine bin received more candidates than it has slots (a plateau of ties)
        SEL_F_HIST = 4 };           // (range records of the scorer) the coarse histogram behind the records is valid for this image

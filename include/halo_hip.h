@@ -298,6 +298,15 @@ int halo_greedy_select(void *score, int dtype, int64_t B, int64_t H, int64_t W, 
                        int64_t *active_mask, const int64_t *gt, double *picks, int32_t *n_picked,
                        void *workspace, size_t workspace_bytes, int method, const void *score_range,
                        int32_t *handover, void *stream);
+/* The sweep places and walks its candidates in two tranches: the top halo_select_first_tranche(...) values of a map first, the
+ * rest of the proven bound n_regions x (2 mask_radius + 1)^2 only for an image whose first tranche ran out before n_regions picks
+ * (a second round inside the same call; results never depend on it).  halo_select_first_tranche: a host query, no device work.
+ * halo_select_stats: the counters of the LAST halo_greedy_select that used `workspace` with the same geometry, copied on `stream`
+ * into stats (B,3) i32: row b = {candidates placed, candidates in the chunks the sweep processed, sweep rounds run (0: the sweep
+ * did not run, 1, or 2)}.  Zeros where the sweep does not serve the geometry. */
+int64_t halo_select_first_tranche(int64_t H, int64_t W, int64_t n_regions, int64_t mask_radius);
+int halo_select_stats(const void *workspace, size_t workspace_bytes, int64_t B, int64_t H, int64_t W, int64_t n_regions,
+                      int64_t mask_radius, int32_t *stats, void *stream);
 
 /* ---- pool side of the round: image-wise sharding, ONE all-gather of pick tables (the reference runs the
  * round on rank 0 only, core/train_learners.py:307-326) ----

@@ -3,7 +3,9 @@
     python tools/sweep_stamps.py --build      # build container: compiles tools/_stamps/libhalo_hip_stamps.so
     python tools/sweep_stamps.py              # GPU box: runs one selection per case and prints the sums
 
-The stamped build writes into the selector header's padding words only (no output value depends on them)."""
+The stamped build writes, in the sweep round that ENDS an image (round A on the smooth map used here; round B returns at once),
+into header words nothing reads after that round: the last four (t1a, nf_a and the two counters) and nvalid / flags / ncand.  No
+output value depends on them; halo_select_stats is meaningless in such a build."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

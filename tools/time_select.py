@@ -1,6 +1,8 @@
 """Timing aid: greedy selection (value-binned sweep vs the serial tile-table kernel) alone and beside the
 streaming feature kernel (one MI355X).  Prints per-call wall time, per-pick time and, with --kernels,
-HIP-event times of the sweep's individual launches (they are issued back to back on one stream)."""
+HIP-event times of the sweep's individual launches (they are issued back to back on one stream).
+The last row is the price of the sweep's second round: a tiled staircase, on which the greedy rule consumes its proven bound of
+(2 mask_radius + 1)^2 candidates per pick, so that the first tranche of candidates runs out for every image."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,11 +16,26 @@ mrad = int(os.environ.get("MRAD", "5"))
 methods = os.environ.get("METHODS", "auto,serial").split(",")
 RANGED = os.environ.get("RANGED", "0") == "1"      # the pipeline's case: the scorer supplied the maps' value range (prepared untimed here)
 from halo_amd import _lib
-from halo_amd.core.active.floating_region import new_score_range
-for B in (1, 4, 16, 32):
+from halo_amd.core.active.floating_region import new_score_range, _workspace
+def staircase(B):
+    """(2r+1)^2 tiles ranked in raster order, value = -(tile x window + rank in tile), rank 0 at the tile's centre (cropped at the border)"""
+    s = 2 * mrad + 1
+    inner = torch.arange(1, s * s + 1, device=dev, dtype=torch.float64)
+    c = mrad * s + mrad
+    inner = torch.where(torch.arange(s * s, device=dev) < c, inner, inner - 1.0)
+    inner[c] = 0.0
+    ty, tx = (H + s - 1) // s, (W + s - 1) // s
+    tile = torch.arange(ty * tx, device=dev, dtype=torch.float64).reshape(ty, tx) * (s * s)
+    m = -(tile.repeat_interleave(s, 0).repeat_interleave(s, 1) + inner.reshape(s, s).repeat(ty, tx))[:H, :W]
+    return m[None].repeat(B, 1, 1).contiguous()
+
+
+for B, kind in ((1, "smooth"), (4, "smooth"), (16, "smooth"), (32, "smooth"), (16, "worst")):
     g = torch.Generator(device=dev).manual_seed(3)
     base = torch.randn((B, H // 4, W // 4), generator=g, device=dev, dtype=torch.float64)
     score0 = torch.nn.functional.interpolate(base[None], size=(H, W), mode="bilinear", align_corners=True)[0].contiguous()
+    if kind == "worst":
+        score0 = staircase(B)
     gt = torch.zeros((B, H, W), dtype=torch.int64, device=dev)
     feat = torch.randn((4, 256, H, W), device=dev, dtype=torch.float64) * 0.01
     logit = torch.randn((4, 19, H, W), device=dev)
@@ -34,6 +51,7 @@ for B in (1, 4, 16, 32):
             act = torch.zeros((B, H, W), dtype=torch.bool, device=dev); sel = torch.zeros_like(act)
             am = torch.full((B, H, W), 255, dtype=torch.int64, device=dev)
             rec = None
+            st = torch.zeros((B, 3), dtype=torch.int32, device=dev)
             if RANGED and method != "serial":
                 rec = new_score_range(B, dev)
                 _lib.check(_lib.lib().halo_score_range(_lib.ptr(sc), _lib.dtype_code(sc), B, H, W, _lib.ptr(rec), _lib.stream_ptr(dev)), "halo_score_range")
@@ -48,7 +66,13 @@ for B in (1, 4, 16, 32):
             hi.synchronize()
             dt = (time.perf_counter() - t0) * 1e3
             torch.cuda.synchronize()
-            return dt, picks, npk
+            if method != "serial":      # the call's counters, read from its workspace OUTSIDE the timed window
+                L = _lib.lib()
+                with torch.cuda.stream(hi):     # (the scratch cache is per stream)
+                    ws = _workspace(dev, L.halo_select_workspace_bytes(B, H, W, n, mrad), "select")
+                    _lib.check(L.halo_select_stats(_lib.ptr(ws), ws.numel(), B, H, W, n, mrad, _lib.ptr(st), _lib.stream_ptr(dev)), "halo_select_stats")
+                torch.cuda.synchronize()
+            return dt, picks, npk, st
         run(False)
         alone = min(run(False)[0] for _ in range(3))
         run(True)
@@ -58,6 +82,8 @@ for B in (1, 4, 16, 32):
         if ref is None:
             ref = picks
         same = bool(torch.equal(ref, picks))
-        print(f"B={B:2d} {method:7s}: alone {alone:7.2f} ms ({alone / n * 1e3:5.2f} us/pick)   beside streaming {loaded:7.2f} ms "
-              f"({loaded / n * 1e3:5.2f} us/pick)   picks {int(npk.min())}..{int(npk.max())}  same as first method: {same}", flush=True)
+        st = res[-1][3].cpu()
+        print(f"B={B:2d} {kind:6s} {method:7s}: alone {alone:7.2f} ms ({alone / n * 1e3:5.2f} us/pick)   beside streaming {loaded:7.2f} ms "
+              f"({loaded / n * 1e3:5.2f} us/pick)   picks {int(npk.min())}..{int(npk.max())}  same as first method: {same}   "
+              f"sweep rounds {int(st[:, 2].min())}..{int(st[:, 2].max())} placed {int(st[:, 0].max())} consumed {int(st[:, 1].max())}", flush=True)
     del feat, logit
