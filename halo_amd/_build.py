@@ -18,7 +18,7 @@ SO = os.path.join(CSRC, "libhalo_hip.so")
 SOURCES = ["halo_api.hip", "halo_score.hip", "halo_select.hip", "halo_select_binned.hip", "halo_hyperbolic.hip", "halo_loss.hip", "halo_pool.hip", "halo_eval.hip", "halo_train_loss.hip", "halo_hfr.hip", "halo_resize.hip", "halo_dwconv.hip", "halo_norm.hip", "halo_norm_autocast.hip", "halo_maxpool.hip", "halo_optim.hip"]
 HOST_SO = os.path.join(CSRC, "libhalo_host.so")          # plain C host helpers (PNG writer of the persistence step), built with gcc
 HOST_SOURCES = ["halo_host.c"]
-HEADERS = ["halo_common.hpp", "halo_norm_dev.hpp", "halo_half_round.hpp", "halo_devmath.hpp", "halo_softmax.hpp", "halo_select_common.hpp", "halo_select_plan.hpp", os.path.join("..", "..", "include", "halo_hip.h")]
+HEADERS = ["halo_common.hpp", "halo_norm_dev.hpp", "halo_half_round.hpp", "halo_half_dev.hpp", "halo_devmath.hpp", "halo_softmax.hpp", "halo_select_common.hpp", "halo_select_plan.hpp", os.path.join("..", "..", "include", "halo_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
 # halo_score.hip: no SLP vectorisation.  Packing the per-class float32 chains of the entropy code into v_pk_* saves 10 % of

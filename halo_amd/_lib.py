@@ -108,6 +108,9 @@ SIGNATURES = {
     "halo_dwconv3x3_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "halo_dwconv3x3_affine_relu_bwd_data": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "halo_dwconv3x3_affine_relu_bwd_weight": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "halo_half_dwconv3x3_affine_relu_fwd": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "halo_half_dwconv3x3_affine_relu_bwd_data": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "halo_half_dwconv3x3_affine_relu_bwd_weight": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp]),
     "halo_multi_dwconv_max_plane": (_i64, []),
     "halo_multi_dwconv3x3_affine_relu_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "halo_multi_dwconv3x3_affine_relu_bwd_data": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),

@@ -31,8 +31,11 @@
 //
 // The ASPP pyramid (halo_multi_dwconv3x3_*): N dilations over one input.  The one place with LDS: a workgroup keeps a plane there
 // and runs the same walk once per dilation (the section in front of the entry points).
+#include <type_traits>
+
 #include "halo_common.hpp"
 #include "halo_devmath.hpp"
+#include "halo_half_dev.hpp"
 #include "halo_softmax.hpp"
 
 namespace halo {
@@ -849,6 +852,289 @@ static int dwm_raise_lds(const char *who,LdsLimitSeen &seen, const void *kernel,
     return HALO_OK;
 }
 
+
+// ---------------------------------------------------------------- the block half under torch.autocast (halo_half_dwconv3x3_*)
+// Under autocast the stock chain casts x and w to half (float16 or bfloat16), the library's half conv returns half, the frozen norm
+// promotes to float32, and autocast rounds the ReLU's result to half again for the pointwise conv.  The same chain walk with every
+// operand in its own element type, h() = round to nearest even to the half dtype DT, half -> float exact:
+//   xh = h(x) (x float32; a half x is read as it is)      wh = h(w[c,k])
+//   c16 = h( sum_k wh[k] xh[tap k] )                      the nine terms in the order above; a product of two halves is exact
+//   pre = fl(fl(float(c16) scale[c]) + shift[c]);  y32 = pre <= 0 ? 0 : pre  (a NaN stays);  y16 = h(y32)      the only output
+//   gp  = y16 > 0 ? fl(float(g16) scale[c]) : 0;   gc16 = h(gp)               the gate is read off y16 (include/halo_hip.h)
+//   g_x = h( sum_k wh[k] gc16[p - k d] )                  stored as half, or widened for a float32 x
+//   g_w[c,k] = float( h( fl32( sum_{b,p} float(gc16) float(xh[p + k d]) ) ) )  float64 fma partials, dw_block_sum, k_dw_wsum's order
+// A window holds the float32 values of halves.  Routes: GW = 4 -- 8-byte accesses of half operands, 16-byte accesses of float32
+// ones, W % 4 == 0 and every operand aligned to its access -- and GW = 1; DwGeom, dw_item and the workspace are the float32 passes'.
+// Conversions: a float -> half rounding behind an fma or a product of widened halves is done in integer arithmetic (ac_round):
+// written as a conversion the compiler folds it into v_fma_mixlo_f16, which rounds the unrounded result once.  Loaded values and
+// the ReLU's result convert in pairs (ac_round_group).
+enum { DH_X = 0, DH_G = 1 };
+
+typedef unsigned short dh_h4 __attribute__((ext_vector_type(4)));
+typedef unsigned short dh_h4u __attribute__((ext_vector_type(4), aligned(2)));
+
+template <bool ALIGNED> __device__ __forceinline__ void dh_load4(const float *p, float *v)
+{
+    dw_f4 t;
+    if constexpr (ALIGNED) t = *reinterpret_cast<const dw_f4 *>(p);
+    else t = *reinterpret_cast<const dw_f4u *>(p);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+}
+
+template <bool ALIGNED> __device__ __forceinline__ void dh_load4(const ac_half *p, ac_half *v)
+{
+    dh_h4 t;
+    if constexpr (ALIGNED) t = *reinterpret_cast<const dh_h4 *>(p);
+    else t = *reinterpret_cast<const dh_h4u *>(p);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+}
+
+// the operand a window is read from, as the float32 value of a half.  KIND DH_X: xh (XT float: h(x); XT ac_half: x).  KIND DH_G:
+// gc16 from a = g16 and y = y16.  cols and row are DwSrc's.
+template <int DT, int KIND, typename XT> struct DhSrc {
+    const XT *a;
+    const ac_half *y;
+    float scale;
+    __device__ __forceinline__ float at(size_t o) const
+    {
+        if constexpr (KIND == DH_X) {
+            if constexpr (sizeof(XT) == 4) return ac_float<DT>(ac_round<DT>(a[o]));
+            else return ac_float<DT>(a[o]);
+        } else {
+            const float p = ac_float<DT>(a[o]) * scale;
+            return ac_float<DT>(ac_round<DT>(ac_float<DT>(y[o]) > 0.0f ? p : 0.0f));
+        }
+    }
+    template <bool ALIGNED> __device__ __forceinline__ void at4(size_t o, float *out) const
+    {
+        if constexpr (KIND == DH_X && sizeof(XT) == 4) {
+            float v[4];
+            ac_half h[4];
+            dh_load4<ALIGNED>(a + o, v);
+            ac_round_group<DT, 4>(v, h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = ac_float<DT>(h[e]);
+        } else if constexpr (KIND == DH_X) {
+            ac_half h[4];
+            dh_load4<ALIGNED>(a + o, h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = ac_float<DT>(h[e]);
+        } else {
+            ac_half gv[4], yv[4];
+            dh_load4<ALIGNED>(a + o, gv);
+            dh_load4<ALIGNED>(y + o, yv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float p = ac_float<DT>(gv[e]) * scale;
+                out[e] = ac_float<DT>(ac_round<DT>(ac_float<DT>(yv[e]) > 0.0f ? p : 0.0f));
+            }
+        }
+    }
+    template <int GW, bool ALIGNED> __device__ __forceinline__ void cols(float *out, int i, int c0, int H, int W) const
+    {
+        const bool row_in = i >= 0 && i < H;
+        const size_t o = (size_t)(row_in ? i : 0) * W;
+        if constexpr (GW == 4) {
+            if (row_in && c0 >= 0 && c0 + 4 <= W) {
+                at4<ALIGNED>(o + c0, out);
+                return;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < GW; ++e) out[e] = row_in && c0 + e >= 0 && c0 + e < W ? at(o + (c0 + e)) : 0.0f;
+    }
+    template <int GW, bool D1> __device__ __forceinline__ void row(float *win, int i, int c0, int H, int W, int d) const
+    {
+        if constexpr (D1 && GW == 4) {
+            cols<4, true>(win + 4, i, c0, H, W);
+            const bool row_in = i >= 0 && i < H;
+            const size_t o = (size_t)(row_in ? i : 0) * W;
+            win[0] = row_in && c0 > 0 ? at(o + (c0 - 1)) : 0.0f;
+            win[1] = win[4], win[2] = win[5], win[3] = win[6];
+            win[8] = win[5], win[9] = win[6], win[10] = win[7];
+            win[11] = row_in && c0 + 4 < W ? at(o + (c0 + 4)) : 0.0f;
+        } else {
+            cols<GW, false>(win, i, c0 - d, H, W);
+            cols<GW, true>(win + GW, i, c0, H, W);
+            cols<GW, false>(win + 2 * GW, i, c0 + d, H, W);
+        }
+    }
+};
+
+template <int DT, int GW> __device__ __forceinline__ void dh_store(ac_half *p, const ac_half *h)
+{
+    if constexpr (GW == 4) {
+        dh_h4 v;
+        v.x = h[0], v.y = h[1], v.z = h[2], v.w = h[3];
+        *reinterpret_cast<dh_h4 *>(p) = v;
+    } else {
+        p[0] = h[0];
+    }
+}
+
+// g_x of a float32 x: the exact widening of the half result
+template <int DT, int GW> __device__ __forceinline__ void dh_store(float *p, const ac_half *h)
+{
+    if constexpr (GW == 4) {
+        dw_f4 v;
+        v.x = ac_float<DT>(h[0]), v.y = ac_float<DT>(h[1]), v.z = ac_float<DT>(h[2]), v.w = ac_float<DT>(h[3]);
+        *reinterpret_cast<dw_f4 *>(p) = v;
+    } else {
+        p[0] = ac_float<DT>(h[0]);
+    }
+}
+
+// dw_walk_apply over typed operands.  MODE DW_FWD: src = xh, op = y16.  MODE DW_BWD: src = gc16, wk mirrored, op = g_x.
+template <int DT, int MODE, int GW, bool D1, typename SRC, typename OT>
+__device__ __forceinline__ void dh_walk_apply(const SRC &src, const float (&wk)[9], float sc, float sh, OT *__restrict__ op, const DwItem &it,
+                                              const DwGeom &G)
+{
+    const int d = D1 ? 1 : G.d;
+    float win[3][3 * GW];
+    src.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
+    src.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
+    for (int i = it.i0; i < it.iend; i += d) {
+        src.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
+        ac_half res[GW];
+        float y32[GW];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            float acc = wk[0] * win[0][e];
+#pragma unroll
+            for (int k = 1; k < 9; ++k) acc = __builtin_fmaf(wk[k], win[k / 3][(k % 3) * GW + e], acc);
+            res[e] = ac_round<DT>(acc);                      // c16, or g_x
+            if constexpr (MODE == DW_FWD) {
+                float pre = ac_float<DT>(res[e]) * sc;
+                pre = pre + sh;
+                y32[e] = pre <= 0.0f ? 0.0f : pre;           // a NaN stays a NaN, as torch's ReLU leaves it
+            }
+        }
+        if constexpr (MODE == DW_FWD) ac_round_group<DT, GW>(y32, res);
+        dh_store<DT, GW>(op + (size_t)i * G.W + it.c0, res);
+#pragma unroll
+        for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
+    }
+}
+
+// the block-uniform taps: wh = h(w[c, k]), mirrored for the data gradient
+template <int DT, int MODE> __device__ __forceinline__ void dh_taps(const float *__restrict__ w, int c, float (&wk)[9])
+{
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wk[k] = ac_float<DT>(ac_round<DT>(MODE == DW_FWD ? w[c * 9 + k] : w[c * 9 + 8 - k]));
+}
+
+template <int DT, typename XT, int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dh_fwd(const XT *__restrict__ x, const float *__restrict__ w, const float *__restrict__ scale,
+                                                   const float *__restrict__ shift, ac_half *__restrict__ y16, DwGeom G)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    DwItem it;
+    if (!dw_item<GW>(G, blk, it)) return;
+    const size_t po = (size_t)plane * G.H * G.W;
+    DhSrc<DT, DH_X, XT> src;
+    src.a = x + po, src.y = nullptr, src.scale = 0.0f;
+    float wk[9];
+    dh_taps<DT, DW_FWD>(w, c, wk);
+    dh_walk_apply<DT, DW_FWD, GW, D1>(src, wk, scale[c], shift[c], y16 + po, it, G);
+}
+
+template <int DT, typename OT, int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dh_bwd(const ac_half *__restrict__ g16, const ac_half *__restrict__ y16, const float *__restrict__ w,
+                                                   const float *__restrict__ scale, OT *__restrict__ g_x, DwGeom G)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    DwItem it;
+    if (!dw_item<GW>(G, blk, it)) return;
+    const size_t po = (size_t)plane * G.H * G.W;
+    DhSrc<DT, DH_G, ac_half> src;
+    src.a = g16 + po, src.y = y16 + po, src.scale = scale[c];
+    float wk[9];
+    dh_taps<DT, DW_BWD>(w, c, wk);
+    dh_walk_apply<DT, DW_BWD, GW, D1>(src, wk, 0.0f, 0.0f, g_x + po, it, G);
+}
+
+// dw_walk_wpart over typed operands: float64 sums of gc16[p] xh[p + k d]
+template <int GW, bool D1, typename SX, typename SG>
+__device__ __forceinline__ void dh_walk_wpart(const SX &sx, const SG &sg, const DwItem &it, const DwGeom &G, double (&acc)[9])
+{
+    const int d = D1 ? 1 : G.d;
+    float win[3][3 * GW];
+    sx.template row<GW, D1>(win[0], it.i0 - d, it.c0, G.H, G.W, d);
+    sx.template row<GW, D1>(win[1], it.i0, it.c0, G.H, G.W, d);
+    for (int i = it.i0; i < it.iend; i += d) {
+        sx.template row<GW, D1>(win[2], i + d, it.c0, G.H, G.W, d);
+        float gp[GW];
+        sg.template cols<GW, true>(gp, i, it.c0, G.H, G.W);
+#pragma unroll
+        for (int e = 0; e < GW; ++e) {
+            const double ge = (double)gp[e];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) acc[k] = __builtin_fma(ge, (double)win[k / 3][(k % 3) * GW + e], acc[k]);
+        }
+#pragma unroll
+        for (int q = 0; q < 3 * GW; ++q) win[0][q] = win[1][q], win[1][q] = win[2][q];
+    }
+}
+
+template <int DT, typename XT, int GW, bool D1>
+__global__ void __launch_bounds__(DW_TPB) k_dh_wpart(const ac_half *__restrict__ g16, const ac_half *__restrict__ y16, const XT *__restrict__ x,
+                                                     const float *__restrict__ scale, double *__restrict__ part, DwGeom G)
+{
+    const long long plane = blockIdx.x / G.bpp;
+    const int blk = (int)(blockIdx.x - plane * G.bpp), c = (int)(plane % G.C);
+    const size_t po = (size_t)plane * G.H * G.W;
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    DwItem it;
+    if (dw_item<GW>(G, blk, it)) {
+        DhSrc<DT, DH_X, XT> sx;
+        sx.a = x + po, sx.y = nullptr, sx.scale = 0.0f;
+        DhSrc<DT, DH_G, ac_half> sg;
+        sg.a = g16 + po, sg.y = y16 + po, sg.scale = scale[c];
+        dh_walk_wpart<GW, D1>(sx, sg, it, G, acc);
+    }
+    dw_block_sum(acc, part);
+}
+
+// k_dw_wsum with the chain's two roundings behind the float64 sum: to float32, then to the half whose value g_w holds
+template <int DT>
+__global__ void __launch_bounds__(DW_TPB) k_dh_wsum(const double *__restrict__ part, float *__restrict__ gw, int B, int C, int bpp)
+{
+    const int e = blockIdx.x * DW_TPB + threadIdx.x;
+    if (e >= C * 9) return;
+    const int c = e / 9, k = e - c * 9;
+    double t = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double *row = part + ((size_t)b * C + c) * bpp * 9 + k;
+        for (int q = 0; q < bpp; ++q) t += row[(size_t)q * 9];
+    }
+    gw[e] = ac_float<DT>(ac_round<DT>((float)t));
+}
+
+static bool dh_half_code(int code) { return code == HALO_F16 || code == HALO_BF16; }
+
+// an operand's alignment for the GW = 4 route: 16 bytes of float32, 8 bytes of half
+static bool dh_aligned(const void *p, int dtype) { return ((uintptr_t)p % (dtype == HALO_F32 ? 16 : 8)) == 0; }
+
+// f(DT, X32, GW, D1) with the run-time choices as types; route 0: <4, true>, 1: <4, false>, 2: <1, false>
+template <class F> static void dh_dispatch(int half_dtype, bool x32, bool vec, int64_t d, F f)
+{
+    auto r = [&](auto DT, auto X32) {
+        if (vec && d == 1) f(DT, X32, std::integral_constant<int, 4>(), std::true_type());
+        else if (vec) f(DT, X32, std::integral_constant<int, 4>(), std::false_type());
+        else f(DT, X32, std::integral_constant<int, 1>(), std::false_type());
+    };
+    auto t = [&](auto DT) {
+        if (x32) r(DT, std::true_type());
+        else r(DT, std::false_type());
+    };
+    if (half_dtype == HALO_BF16) t(std::integral_constant<int, HALO_BF16>());
+    else t(std::integral_constant<int, HALO_F16>());
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -1117,5 +1403,74 @@ extern "C" int halo_fan_dwconv3x3_affine_relu_bwd_data(const float *const *g, co
         if (int rc = dwm_raise_lds(who, seen1, (const void *)k_dwm_fan_bwd<1>, lds)) return rc;
         hipLaunchKernelGGL((k_dwm_fan_bwd<1>), gr, bl, lds, st, y, w, scale, g_x, P, F, (long long)planes);
     }
+    return check_launch(who);
+}
+
+extern "C" int halo_half_dwconv3x3_affine_relu_fwd(const void *x, int x_dtype, const float *w, const float *scale, const float *shift, void *y16,
+                                                   int half_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d, void *stream)
+{
+    const char *who = "halo_half_dwconv3x3_affine_relu_fwd";
+    if (!x || !w || !scale || !shift || !y16) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (!dh_half_code(half_dtype)) return fail(HALO_E_ARG, "%s: half_dtype %d is neither HALO_F16 nor HALO_BF16", who, half_dtype);
+    if (x_dtype != HALO_F32 && x_dtype != half_dtype) return fail(HALO_E_ARG, "%s: x_dtype %d is neither HALO_F32 nor half_dtype", who, x_dtype);
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    const bool vec = W % 4 == 0 && dh_aligned(x, x_dtype) && dh_aligned(y16, half_dtype);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    dh_dispatch(half_dtype, x_dtype == HALO_F32, vec, d, [&](auto DT, auto X32, auto GW, auto D1) {
+        using XT = std::conditional_t<decltype(X32)::value, float, ac_half>;
+        hipLaunchKernelGGL((k_dh_fwd<decltype(DT)::value, XT, decltype(GW)::value, decltype(D1)::value>), dim3(grid), dim3(DW_TPB), 0,
+                           (hipStream_t)stream, (const XT *)x, w, scale, shift, (ac_half *)y16, G);
+    });
+    return check_launch(who);
+}
+
+extern "C" int halo_half_dwconv3x3_affine_relu_bwd_data(const void *g16, const void *y16, const float *w, const float *scale, void *g_x,
+                                                        int gx_dtype, int half_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d,
+                                                        void *stream)
+{
+    const char *who = "halo_half_dwconv3x3_affine_relu_bwd_data";
+    if (!g16 || !y16 || !w || !scale || !g_x) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (!dh_half_code(half_dtype)) return fail(HALO_E_ARG, "%s: half_dtype %d is neither HALO_F16 nor HALO_BF16", who, half_dtype);
+    if (gx_dtype != HALO_F32 && gx_dtype != half_dtype) return fail(HALO_E_ARG, "%s: gx_dtype %d is neither HALO_F32 nor half_dtype", who, gx_dtype);
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    const bool vec = W % 4 == 0 && dh_aligned(g16, half_dtype) && dh_aligned(y16, half_dtype) && dh_aligned(g_x, gx_dtype);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    dh_dispatch(half_dtype, gx_dtype == HALO_F32, vec, d, [&](auto DT, auto X32, auto GW, auto D1) {
+        using OT = std::conditional_t<decltype(X32)::value, float, ac_half>;
+        hipLaunchKernelGGL((k_dh_bwd<decltype(DT)::value, OT, decltype(GW)::value, decltype(D1)::value>), dim3(grid), dim3(DW_TPB), 0,
+                           (hipStream_t)stream, (const ac_half *)g16, (const ac_half *)y16, w, scale, (OT *)g_x, G);
+    });
+    return check_launch(who);
+}
+
+extern "C" int halo_half_dwconv3x3_affine_relu_bwd_weight(const void *g16, const void *y16, const void *x, int x_dtype, const float *scale,
+                                                          float *g_w, int half_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d,
+                                                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "halo_half_dwconv3x3_affine_relu_bwd_weight";
+    if (!g16 || !y16 || !x || !scale || !g_w) return fail(HALO_E_ARG, "%s: null argument", who);
+    if (!dh_half_code(half_dtype)) return fail(HALO_E_ARG, "%s: half_dtype %d is neither HALO_F16 nor HALO_BF16", who, half_dtype);
+    if (x_dtype != HALO_F32 && x_dtype != half_dtype) return fail(HALO_E_ARG, "%s: x_dtype %d is neither HALO_F32 nor half_dtype", who, x_dtype);
+    if (int rc = dw_check(who, B, C, H, W, d)) return rc;
+    const size_t need = halo_dwconv_workspace_bytes(B, C, H, W, d);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 8) != 0)
+        return fail(HALO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (8-byte aligned)", who, workspace_bytes, need);
+    const bool vec = W % 4 == 0 && dh_aligned(g16, half_dtype) && dh_aligned(y16, half_dtype) && dh_aligned(x, x_dtype);
+    const DwGeom G = dw_geom(C, H, W, d, vec ? 4 : 1);
+    unsigned grid;
+    if (int rc = dw_grid(who, B * C, G, grid)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    dh_dispatch(half_dtype, x_dtype == HALO_F32, vec, d, [&](auto DT, auto X32, auto GW, auto D1) {
+        using XT = std::conditional_t<decltype(X32)::value, float, ac_half>;
+        hipLaunchKernelGGL((k_dh_wpart<decltype(DT)::value, XT, decltype(GW)::value, decltype(D1)::value>), dim3(grid), dim3(DW_TPB), 0, st,
+                           (const ac_half *)g16, (const ac_half *)y16, (const XT *)x, scale, part, G);
+        hipLaunchKernelGGL((k_dh_wsum<decltype(DT)::value>), dim3((unsigned)cdiv(C * 9, DW_TPB)), dim3(DW_TPB), 0, st, (const double *)part, g_w,
+                           (int)B, (int)C, G.bpp);
+    });
     return check_launch(who);
 }

@@ -18,7 +18,8 @@ eval mode with running statistics whose parameters need no gradient: scale = wei
 
 Anything outside the served envelope (fallback_reason) runs the three stock module calls (torch_statement), so torch's results
 and errors are kept there: batch statistics, a conv bias, other kernel sizes / strides / padding, other dtypes, autocast, CPU
-tensors.
+tensors.  Under torch.autocast `depthwise_bn_relu_autocast(x, conv, bn)` serves the same block half with a float32 or half x and
+the half output autocast would hand the pointwise conv (the section behind depthwise_bn_relu; halo_amd.hooks.use_autocast_depthwise).
 
 The front of the v3+ decoder feeds such a block with `torch.cat([resize(a, s.shape[2:]), s], 1)`.
 `upsample_cat_depthwise_bn_relu(a, s, conv, bn)` computes that block's depthwise half without storing the resized or the
@@ -249,6 +250,125 @@ def depthwise_bn_relu(x, conv, bn, act=None, joint_backward=False):
     scale, shift = scale_shift(bn)
     fn = _DepthwiseBnReluFnJoint if joint_backward and joint_fallback_reason(x, conv, bn) is None else _DepthwiseBnReluFn
     return fn.apply(x.contiguous(), conv.weight.contiguous(), scale, shift, int(_pair(conv.dilation)[0]))
+
+
+# ---------------------------------------------------------------- the block half under torch.autocast
+# Under autocast the stock statements cast x and the conv's weight to half (float16 or bfloat16), the library's half conv returns
+# half, the frozen norm promotes to float32, the ReLU stays float32 and autocast rounds its result to half in front of the pointwise
+# conv: six passes where depthwise_bn_relu_autocast makes one (halo_half_dwconv3x3_* of halo_dwconv.hip: x float32 or half in, y16
+# out, every stage rounded where the chain rounds it).  The node's only output is y16 = what autocast's cast would hand the
+# pointwise conv; its backward keeps x, y16, w and scale and reads the ReLU's gate off y16 (include/halo_hip.h: where 0 < y32 rounds
+# to a half zero the gradient is 0, autograd's passes; the pointwise conv saw 0 there on both sides).  As with depthwise_bn_relu
+# the sums are the chain walk's, not the library conv's bits.
+
+autocast_launches = {"fwd": 0, "bwd_data": 0, "bwd_weight": 0}
+
+
+def _half_code(dtype):
+    return {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}.get(dtype)
+
+
+def _autocast_dtype():
+    from .norm import _autocast_dtype as device_autocast_dtype
+    return device_autocast_dtype()
+
+
+def autocast_statement(x, conv, bn, act=None):
+    """torch_statement under the current autocast state, then the cast autocast makes in front of the pointwise conv (to the
+    device's autocast dtype; to a half x's own dtype, i.e. nothing, with autocast off).  The fallback of
+    depthwise_bn_relu_autocast and the stock side of its tests and timings."""
+    dt = _autocast_dtype()
+    y = torch_statement(x, conv, bn, act)
+    return y.to(dt) if dt is not None and y.is_floating_point() else y
+
+
+def autocast_fallback_reason(x, conv, bn):
+    """why depthwise_bn_relu_autocast(x, conv, bn) runs autocast_statement (None: the fused pass serves it).  Reads no device
+    memory."""
+    why, tensors = _module_reason(conv, bn)
+    if why is not None:
+        return why
+    if not torch.is_tensor(x) or x.dim() != 4:
+        return "x is not a (B, C, H, W) tensor"
+    dt = _autocast_dtype()
+    if dt is None:
+        return "autocast is not enabled on the device"
+    if _half_code(dt) is None:
+        return "the autocast dtype is %s, not float16 or bfloat16" % dt
+    if not _is_frozen(bn):                 # nn.BatchNorm2d on a half input is the library's batch norm: one rounding, another chain
+        return "under autocast the norm must be a FrozenBatchNorm2d, whose statements promote to float32"
+    C, dil = conv.in_channels, _pair(conv.dilation)
+    if x.shape[1] != C:
+        return "x has %d channels, the conv %d" % (x.shape[1], C)
+    if x.dtype != torch.float32 and x.dtype != dt:
+        return "x is %s, neither float32 nor the autocast dtype %s" % (x.dtype, dt)
+    if not x.is_cuda:
+        return "x is not on a ROCm device"
+    if not x.is_contiguous():
+        return "x is not contiguous NCHW"
+    for t in [conv.weight] + tensors:
+        if t is not None and (t.dtype != torch.float32 or t.device != x.device):
+            return "a conv / norm tensor is not float32 on %s" % x.device
+    B, _, H, W = x.shape
+    if B * C * H * W == 0:
+        return "empty input"
+    if max(H, W, dil[0]) > 1 << 24 or H * W > 2 ** 31 - 1:
+        return "plane of %d x %d, dilation %d" % (H, W, dil[0])
+    return None
+
+
+class _DepthwiseBnReluAutocastFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, scale, shift, d, half):
+        B, C, H, W = x.shape
+        code = _half_code(half)
+        y16 = torch.empty(x.shape, dtype=half, device=x.device)
+        _lib.check(_lib.lib().halo_half_dwconv3x3_affine_relu_fwd(_lib.ptr(x), _lib.F32 if x.dtype == torch.float32 else code, _lib.ptr(w),
+                                                                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y16), code, B, C, H, W, d,
+                                                                  _lib.stream_ptr(x.device)), "halo_half_dwconv3x3_affine_relu_fwd")
+        autocast_launches["fwd"] += 1
+        ctx.save_for_backward(x, y16, w, scale)
+        ctx.d, ctx.half = d, half
+        return y16
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, y16, w, scale = ctx.saved_tensors
+        B, C, H, W = x.shape
+        d, code = ctx.d, _half_code(ctx.half)
+        x_code = _lib.F32 if x.dtype == torch.float32 else code
+        L = _lib.lib()
+        st = _lib.stream_ptr(x.device)
+        g = g.to(device=x.device, dtype=ctx.half).contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            _lib.check(L.halo_half_dwconv3x3_affine_relu_bwd_data(_lib.ptr(g), _lib.ptr(y16), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(gx), x_code,
+                                                                  code, B, C, H, W, d, st), "halo_half_dwconv3x3_affine_relu_bwd_data")
+            autocast_launches["bwd_data"] += 1
+        if ctx.needs_input_grad[1]:
+            nws = L.halo_dwconv_workspace_bytes(B, C, H, W, d)
+            ws = torch.empty(max(nws // 8, 1), dtype=torch.float64, device=x.device)
+            gw = torch.empty_like(w)
+            _lib.check(L.halo_half_dwconv3x3_affine_relu_bwd_weight(_lib.ptr(g), _lib.ptr(y16), _lib.ptr(x), x_code, _lib.ptr(scale), _lib.ptr(gw),
+                                                                    code, B, C, H, W, d, _lib.ptr(ws), ws.numel() * 8, st),
+                       "halo_half_dwconv3x3_affine_relu_bwd_weight")
+            autocast_launches["bwd_weight"] += 1
+        return gx, gw, None, None, None, None
+
+
+def depthwise_bn_relu_autocast(x, conv, bn, act=None):
+    """relu(bn(conv(x))) of a depthwise 3x3 conv and a frozen / eval-mode norm under torch.autocast, rounded to the autocast dtype
+    as the cast in front of the next convolution rounds it: y16 (B, C, H, W), float16 or bfloat16, for an x that is float32 or
+    that dtype.  Differentiable once w.r.t. x (the gradient has x's dtype and holds half values) and conv.weight (float32, a
+    half's value).  Every stage is rounded where the stock chain rounds it; the nine-term sums are the chain walk's, so a result
+    is the stock chain's except where a sum lies within the float32 accumulation error of a half rounding boundary, and then its
+    neighbour.  Outside the served envelope (autocast_fallback_reason) it returns autocast_statement(x, conv, bn, act)."""
+    if autocast_fallback_reason(x, conv, bn) is not None:
+        return autocast_statement(x, conv, bn, act)
+    scale, shift = scale_shift(bn)
+    return _DepthwiseBnReluAutocastFn.apply(x, conv.weight.contiguous(), scale, shift, int(_pair(conv.dilation)[0]), _autocast_dtype())
 
 
 def upcat_fallback_reason(a, s, conv, bn):
@@ -494,4 +614,5 @@ def multi_depthwise_bn_relu(x, blocks):
 
 __all__ = ["depthwise_bn_relu", "torch_statement", "fallback_reason", "scale_shift", "upsample_cat_depthwise_bn_relu", "upcat_fallback_reason",
            "multi_depthwise_bn_relu", "multi_fallback_reason", "multi_max_plane", "launches", "joint_fallback_reason",
-           "upcat_joint_fallback_reason", "joint_launches", "JOINT_MIN_ELEMENTS"]
+           "upcat_joint_fallback_reason", "joint_launches", "JOINT_MIN_ELEMENTS", "depthwise_bn_relu_autocast", "autocast_fallback_reason",
+           "autocast_statement", "autocast_launches"]

@@ -402,8 +402,23 @@ def use_device_resize(cls):
 _DWSEP_ATTRS = ("depthwise_conv", "depthwise_bn", "depthwise_activate", "pointwise_conv", "pointwise_bn", "pointwise_activate")
 
 
+def _autocast_depthwise(block, x):
+    """a block of a class marked by use_autocast_depthwise, under torch.autocast, where halo_amd.dwconv.autocast_fallback_reason
+    holds: its depthwise half from halo_amd.dwconv.depthwise_bn_relu_autocast (half, what autocast's cast would hand pointwise_conv);
+    None otherwise"""
+    if not getattr(type(block), "_halo_autocast_depthwise", False) or type(block.depthwise_activate) is not torch.nn.ReLU:
+        return None
+    from .dwconv import autocast_fallback_reason, depthwise_bn_relu_autocast
+    if autocast_fallback_reason(x, block.depthwise_conv, block.depthwise_bn) is not None:
+        return None
+    return depthwise_bn_relu_autocast(x, block.depthwise_conv, block.depthwise_bn, block.depthwise_activate)
+
+
 def fused_dwsep_forward(self, x):
     from .dwconv import depthwise_bn_relu, torch_statement
+    half = _autocast_depthwise(self, x)
+    if half is not None:
+        return pointwise_tail(self, half)
     if type(self.depthwise_activate) is torch.nn.ReLU:
         x = depthwise_bn_relu(x, self.depthwise_conv, self.depthwise_bn, self.depthwise_activate,
                               joint_backward=getattr(type(self), "_halo_joint_depthwise_backward", False))
@@ -437,6 +452,25 @@ def use_fused_depthwise(block_cls):
         return block_cls
     block_cls._unfused_forward = _inherited(block_cls, "forward")
     block_cls.forward = fused_dwsep_forward
+    return block_cls
+
+
+# ---------------------------------------------------------------- the same half under torch.autocast
+# precision=16 runs the heads under torch.autocast, where depthwise_bn_relu steps aside ("autocast is enabled") and the stock chain
+# makes six passes.  `use_autocast_depthwise(block_cls)` marks a class that use_fused_depthwise has bound: under autocast, where
+# halo_amd.dwconv.autocast_fallback_reason holds, fused_dwsep_forward and depthwise_half run
+# halo_amd.dwconv.depthwise_bn_relu_autocast -- float32 or half in, half out -- and hand its result to pointwise_conv.  A mark of
+# its own, not behaviour of use_fused_depthwise: the pass rounds every stage where the stock chain does, but its nine-term sums
+# are the chain walk's, not the library's half conv's bits.  With autocast off a marked class does exactly what it did.  Not bound
+# by install().  The decoder front, the LDS pyramid, the joint backward and the dropout tail keep stepping aside under autocast.
+
+def use_autocast_depthwise(block_cls):
+    """Mark a depthwise-separable block class under use_fused_depthwise so that its depthwise half runs
+    halo_amd.dwconv.depthwise_bn_relu_autocast under torch.autocast.  Returns the class.  Idempotent.  TypeError for a class
+    whose forward is not fused_dwsep_forward."""
+    if not isinstance(block_cls, type) or _inherited(block_cls, "forward") is not fused_dwsep_forward:
+        raise TypeError("use_autocast_depthwise: %r is not a class under use_fused_depthwise; bind that first" % (block_cls,))
+    block_cls._halo_autocast_depthwise = True
     return block_cls
 
 
@@ -894,11 +928,11 @@ def unfuse_norm_relu_pool(module):
 
 def pointwise_tail(block, x):
     """the second half of a separable block from its depthwise half's output: the three pointwise modules, or -- on a class marked by
-    use_fused_pointwise_norm whose pointwise_activate is an nn.ReLU -- the conv and halo_amd.norm.norm_relu"""
+    use_fused_pointwise_norm whose pointwise_activate is an nn.ReLU -- the conv and halo_amd.norm.norm_relu (under torch.autocast,
+    where its envelope holds, halo_amd.norm.norm_relu_autocast with the float32 output)"""
     x = block.pointwise_conv(x)
     if getattr(type(block), "_halo_fused_pointwise_norm", False) and type(block.pointwise_activate) is torch.nn.ReLU:
-        from .norm import norm_relu
-        return norm_relu(x, block.pointwise_bn)
+        return _norm_relu_either(x, block.pointwise_bn)      # under torch.autocast: norm_relu_autocast's float32, the stock chain's bits
     x = block.pointwise_bn(x)
     x = block.pointwise_activate(x)
     return x
@@ -943,6 +977,9 @@ def depthwise_half(block, x):
     use_fused_depthwise, the three stock statements otherwise"""
     if _inherited(type(block), "forward") is fused_dwsep_forward and type(block.depthwise_activate) is torch.nn.ReLU:
         from .dwconv import depthwise_bn_relu
+        half = _autocast_depthwise(block, x)
+        if half is not None:
+            return half
         return depthwise_bn_relu(x, block.depthwise_conv, block.depthwise_bn, block.depthwise_activate,
                                  joint_backward=getattr(type(block), "_halo_joint_depthwise_backward", False))
     return block.depthwise_activate(block.depthwise_bn(block.depthwise_conv(x)))

@@ -517,6 +517,31 @@ int halo_joint_upcat_dwconv3x3_affine_relu_bwd(const float *g, const float *y, c
                                                int64_t h, int64_t w_in, int64_t H, int64_t W, void *workspace, size_t workspace_bytes,
                                                void *stream);
 
+/* ---- the same block half under torch.autocast: half in, half out (halo_amd/dwconv.py: depthwise_bn_relu_autocast) ----
+ *  half_dtype = HALO_F16 | HALO_BF16 is the element type of y16 and g16; x (x_dtype) and g_x (gx_dtype) are HALO_F32 or half_dtype;
+ *  w, scale, shift and g_w are float32.  All activations (B, C, H, W) dense NCHW.  h() rounds to nearest even to half_dtype
+ *  (overflow to +-inf, a NaN stays a NaN), half -> float is exact:
+ *    xh = h(x) (the identity for a half x);  wh = h(w[c,k]);  c16 = h(sum_k wh[k] xh[tap k])
+ *    pre = fl(fl(float(c16) scale[c]) + shift[c]);  y32 = pre <= 0 ? 0 : pre (a NaN stays a NaN);  y16 = h(y32), the only output
+ *    gp = y16 > 0 ? fl(float(g16) scale[c]) : 0;  gc16 = h(gp);  g_x = h(sum_k wh[k] gc16[p - k d]), widened for gx_dtype HALO_F32
+ *    g_w[c,k] = float(h(fl32(sum_{b,p} float(gc16) float(xh[p + k d]))))
+ *  the stages and roundings of `conv(x); x * scale + bias; relu_; .to(half)` under autocast and of its autograd backward, with one
+ *  deviation: the gate is read off y16, so where 0 < y32 rounds to a half zero the gradient is 0 and autograd's passes.  The sums
+ *  are the float32 passes': nine terms in ascending input position, the first product rounded, one fma each (a product of two
+ *  halves is exact in float32); g_w in float64 partials and halo_dwconv_workspace_bytes(B, C, H, W, d) of workspace, no atomics.
+ *  The bits depend on the operands and the shape alone.  They are not the library convolution's: a sum within the float32
+ *  accumulation error of a half rounding boundary may land on the other neighbour.  W % 4 == 0 with every float32 activation
+ *  16-byte and every half activation 8-byte aligned runs four columns per thread, anything else one.  Checks before any launch:
+ *  HALO_E_ARG for a missing pointer, a half_dtype outside {HALO_F16, HALO_BF16}, an x_dtype / gx_dtype outside {HALO_F32,
+ *  half_dtype}, an empty shape or d < 1; HALO_E_UNSUPPORTED for the limits above; HALO_E_WORKSPACE for a short workspace. */
+int halo_half_dwconv3x3_affine_relu_fwd(const void *x, int x_dtype, const float *w, const float *scale, const float *shift, void *y16,
+                                        int half_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d, void *stream);
+int halo_half_dwconv3x3_affine_relu_bwd_data(const void *g16, const void *y16, const float *w, const float *scale, void *g_x, int gx_dtype,
+                                             int half_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d, void *stream);
+int halo_half_dwconv3x3_affine_relu_bwd_weight(const void *g16, const void *y16, const void *x, int x_dtype, const float *scale, float *g_w,
+                                               int half_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t d, void *workspace,
+                                               size_t workspace_bytes, void *stream);
+
 /* ---- frozen norm + residual add + ReLU of a ResNet block(core/models/resnet.py:53-69, 92-112; core/models/layers.py) ----
  *  x, r, y, g, g_x, g_r (B, C, HW) f32 dense NCHW planes; scale, shift, r_scale, r_shift (C) f32.
  *    pre = fl(fl(x scale[c]) + shift[c]);  id = r  or  fl(fl(r r_scale[c]) + r_shift[c]);  y = relu(pre)  or  relu(fl(pre + id))
